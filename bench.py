@@ -16,13 +16,26 @@ all-reduce of the gradients.
 `value` is the whole job's throughput (all ranks' tokens / max-over-ranks
 time, weak scaling: B=8 per GPU); `value_per_gpu` = value / N.
 
-Every N: `scan_scaling` -- the north-star selective_scan forward (B=32,
+A plain run does only what the headline needs: set-up, W warm-up steps, K
+timed steps, the JSON line (with `step_mfma`, derived from the step time).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+step computed as DIR/<name>.npy (float32): `loss`, `logits` [B, T, vocab], and
+a fixed seeded sample (DUMP_PER_TENSOR elements of every parameter, in
+model.parameters() order, concatenated) of the gradients the step left
+(`grads_sample`) and of the parameters after its optimizer update
+(`params_sample`).  Weights and batch are seeded, so two builds run with the
+same arguments see identical inputs.
+
+--full adds every other leg to the same JSON line.
+
+--full, every N: `scan_scaling` -- the north-star selective_scan forward (B=32,
 L=8192, d_inner=2048, fp32 I/O) as a second scaling leg, no collective on the
 data path: "weak" (every rank scans its own B=32 batch) and "strong" (the
 B=32 batch sharded 32/N rows per rank); bytes of all ranks / max-over-ranks
-time.
+time.  N > 1: `dp`, the data-parallel breakdown (dp_breakdown).
 
-Also reported on rank 0 at N = 1 (same JSON line):
+--full, on rank 0 at N = 1 (same JSON line):
   roofline      selective_scan fwd at the north-star shape (B=32, L=8192,
                 d_inner=2048, N=16) with fp32 I/O -- the reference's own
                 precision (train.py runs mamba-ssm in fp32) -- HIP-event
@@ -89,6 +102,37 @@ def make_batch(c, dev, seed):
     return tokens, text, z, mask
 
 
+DUMP_PER_TENSOR = 8192   # sampled elements per parameter tensor (--dump-outputs)
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, loss, logits, params):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files
+    (module docstring).  The sample takes every element of a parameter of up to
+    DUMP_PER_TENSOR elements, else DUMP_PER_TENSOR of them at indices drawn once
+    from a CPU generator seeded with DUMP_SEED + the parameter's position, so
+    the same elements are taken in every run and by every build (C2: 1.37 M
+    elements = 5.5 MB per sample file, 12 MB in all)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    grads, vals = [], []
+    for i, p in enumerate(params):
+        n = p.numel()
+        flat_p = p.detach().reshape(-1)
+        flat_g = torch.zeros_like(flat_p) if p.grad is None else p.grad.detach().reshape(-1)   # unused parameter
+        if n > DUMP_PER_TENSOR:
+            g = torch.Generator().manual_seed(DUMP_SEED + i)
+            idx = torch.randint(0, n, (DUMP_PER_TENSOR,), generator=g).to(p.device)
+            flat_p, flat_g = flat_p[idx], flat_g[idx]
+        vals.append(flat_p.float().cpu())
+        grads.append(flat_g.float().cpu())
+    out = {"loss": loss.detach().float().reshape(1).cpu(), "logits": logits.detach().float().cpu(),
+           "grads_sample": torch.cat(grads), "params_sample": torch.cat(vals)}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy().astype(np.float32, copy=False))
+    log(f"[bench] wrote {', '.join(f'{k}.npy {tuple(v.shape)}' for k, v in out.items())} to {path}")
+
+
 def train_bench(args, rank, world, dev):
     import mamba_decoder
     from mtts.optim import FusedClipAdam
@@ -120,7 +164,7 @@ def train_bench(args, rank, world, dev):
         if dp is not None:
             dp.finish()
         opt.step()
-        return loss
+        return loss, logits
 
     first_loss = None
     run = step
@@ -133,28 +177,28 @@ def train_bench(args, rank, world, dev):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(max(args.warmup, 1)):
-                l0 = step()
+                l0, _ = step()
                 first_loss = float(l0.item()) if first_loss is None else first_loss
             del l0
         torch.cuda.current_stream().wait_stream(side)
         opt.zero_grad(set_to_none=True)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            static_loss = step()
+            static_out = step()
 
         def run():
             graph.replay()
-            return static_loss
+            return static_out
     else:
         for _ in range(args.warmup):
-            l0 = step()
+            l0, _ = step()
             first_loss = float(l0.item()) if first_loss is None else first_loss
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = run()
+        loss, logits = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -164,8 +208,10 @@ def train_bench(args, rank, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     assert torch.isfinite(loss).item(), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, logits, params)
     dpinfo = None
-    if dp is not None:
+    if dp is not None and args.full:
         dpinfo = dp_breakdown(lambda: cross_entropy(model(tokens, text, z, text_mask=mask).view(-1, c["vocab"]),
                                                     tokens.view(-1), ignore_index=0), dp, dev)
         log(f"[bench] data parallel: {dpinfo}")
@@ -633,7 +679,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--decode-steps", type=int, default=4096)   # C4: 4096-step AR loop
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--skip-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (scan roofline and scaling, C5 step, text encoder, style, decode, "
+                         "CPU baselines, N > 1: data-parallel breakdown); off: only the headline's timed steps")
+    ap.add_argument("--skip-extras", action="store_true",
+                    help="with --full: keep the scan scaling leg (and N > 1 breakdown), skip the other legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits and a seeded sample of gradients and updated "
+                         "parameters to DIR/<name>.npy (float32)")
     ap.add_argument("--graph", type=int, default=0,
                     help="1: replay the training step as one captured hipGraph (equal speed here: the step is GPU-bound)")
     ap.add_argument("--launch-check", action="store_true",
@@ -663,11 +716,12 @@ def main():
 
     # the roofline kernel is timed first, on the chip as the driver hands it over
     # (after the C2 training loop the same launches measure ~5-7 % slower: clocks)
+    extras = args.full and not args.skip_extras
     roof = None
-    if rank == 0 and world == 1 and not args.skip_extras:
+    if rank == 0 and world == 1 and extras:
         roof = (scan_roofline(torch.float32), scan_roofline(torch.bfloat16))
     c, ms, tps, loss, dpinfo = train_bench(args, rank, world, dev)
-    scaling_leg = scan_scaling(rank, world, dev)
+    scaling_leg = scan_scaling(rank, world, dev) if args.full else None
     log(f"[bench] step {ms:.2f} ms  {tps:.0f} tok/s  loss first warmup step {loss[0]} -> last timed step {loss[1]:.3e} "
         f"(one fixed batch; the decoder's unshifted targets, SURVEY quirk 4, make it learn the identity fast)")
     rec = {
@@ -684,16 +738,17 @@ def main():
     fl = flops_per_step(c)
     rec["step_mfma"] = {"bound": "mfma", "achieved": fl / (ms * 1e-3) / 1e12, "peak": BF16_PEAK / 1e12,
                         "unit": "TFLOP/s", "frac": fl / (ms * 1e-3) / BF16_PEAK, "flops_per_step": fl}
-    rec["scan_scaling"] = scaling_leg
+    if scaling_leg is not None:
+        rec["scan_scaling"] = scaling_leg
     if dpinfo is not None:
         rec["dp"] = dpinfo
-    if roof is None:
+    if roof is None and scaling_leg is not None:
         # N > 1 (or --skip-extras): the roofline kernel's per-GPU figure from the
         # weak leg (each rank ran the full north-star batch; slowest rank)
         wk = scaling_leg["weak"]
         nb = wk["GB_per_s"] * 1e9 * wk["ms_per_launch"] * 1e-3 / world
         roof = ((wk["ms_per_launch"], nb, nb / (wk["ms_per_launch"] * 1e-3)), None)
-    if rank == 0:
+    if rank == 0 and roof is not None:
         (fms, fb, fbw) = roof[0]
         log(f"[bench] scan fp32 north-star {fms:.3f} ms {fbw / 1e9:.0f} GB/s")
         rec["roofline"] = {"kernel": "selective_scan_fwd (north-star B=32 L=8192 d_inner=2048 N=16, fp32 I/O = the "
@@ -708,10 +763,10 @@ def main():
             rec["roofline_bf16"] = {"bound": "hbm (VALU-limited, DESIGN.md section 3)", "achieved": sbw / 1e9,
                                     "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": sbw / HBM_PEAK, "ms": sms,
                                     "algorithmic_bytes": sb, "traffic": pmc_traffic("bf16")}
-    if not args.skip_extras:
+    if extras:
         rec["c5_step"] = c5_step_bench(rank, world, dev)
         log(f"[bench] c5 step {rec['c5_step']}")
-    if rank == 0 and world == 1 and not args.skip_extras:
+    if rank == 0 and world == 1 and extras:
         rec["text_encoder"] = text_bench()
         log(f"[bench] text encoder {rec['text_encoder']}")
         rec["style"] = style_bench()

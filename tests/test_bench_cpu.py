@@ -35,3 +35,36 @@ def test_bench_launches_two_ranks():
 
 def test_bench_single_rank_needs_no_launcher():
     assert _run(1)["n_gpus"] == 1
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: loss, logits whole; parameters and gradients whole up to
+    DUMP_PER_TENSOR elements, else the same DUMP_PER_TENSOR seeded elements in
+    every call (so two builds can be compared output for output)."""
+    import numpy as np
+    import torch
+    import bench
+    k = bench.DUMP_PER_TENSOR
+    g = torch.Generator().manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(3 * k + 5, generator=g)), torch.nn.Parameter(torch.randn(7, 3, generator=g)),
+              torch.nn.Parameter(torch.randn(4, generator=g))]
+    params[0].grad = torch.randn(3 * k + 5, generator=g)
+    params[1].grad = torch.randn(7, 3, generator=g)          # params[2]: unused, no gradient
+    loss = torch.tensor(1.25, dtype=torch.float64)
+    logits = torch.randn(2, 5, 10, generator=g).to(torch.bfloat16)
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, logits, params)
+        assert sorted(os.listdir(tmp_path / d)) == ["grads_sample.npy", "logits.npy", "loss.npy", "params_sample.npy"]
+        got.append({n: np.load(tmp_path / d / (n + ".npy")) for n in ("loss", "logits", "grads_sample", "params_sample")})
+    a, b = got
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert a["loss"].tolist() == [1.25] and np.array_equal(a["logits"], logits.float().numpy())
+    assert a["params_sample"].shape == a["grads_sample"].shape == (k + 21 + 4,)
+    # the small tensors are whole and in order; the large one's sample holds its own elements, pairwise with its grads
+    assert np.array_equal(a["params_sample"][k:k + 21], params[1].detach().reshape(-1).numpy())
+    assert np.array_equal(a["grads_sample"][k:k + 21], params[1].grad.reshape(-1).numpy())
+    assert np.array_equal(a["grads_sample"][k + 21:], np.zeros(4, np.float32))
+    lookup = {float(p): float(gr) for p, gr in zip(params[0].detach().tolist(), params[0].grad.tolist())}
+    assert all(lookup[float(p)] == float(gr) for p, gr in zip(a["params_sample"][:k], a["grads_sample"][:k]))
