@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTTS_ABI_VERSION 14
+#define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
 enum {
@@ -782,6 +782,60 @@ typedef struct {
 } MttsDropoutArgs;
 
 int mtts_dropout(const MttsDropoutArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Token sampler (ABI 15; csrc/sample.hip): one launch turns a (rows, vocab)
+ * logits matrix into one token per row -- the end of an autoregressive step
+ * (mamba_decoder.py:188-256 returns logits; the caller's argmax / multinomial
+ * loop around it is what this replaces).  With x_v = logit_v + bias_v (the
+ * sum taken in fp32; NaN counts as -inf):
+ *   temperature == 0: argmax_v x_v, lowest index on ties, no random numbers;
+ *   top_k > 0:        keep v iff #{w : x_w > x_v} < top_k (threshold ties kept);
+ *   0 < top_p < 1:    with p = softmax(x / T) over the top-k survivors, keep v
+ *                     iff sum_{w : p_w > p_v} p_w < top_p;
+ *   draw:             argmax_v (x_v / T + g_v) over the kept set, lowest index
+ *                     on ties, g_v = -log(-log(u_v)), u_v = ((h >> 40) + 0.5) *
+ *                     2^-24, h = splitmix64-finalizer(seed + c * 0x9E3779B97F4A7C15),
+ *                     c = (step * rows + row) * vocab + v  (64-bit).
+ * `seed` and `step` live in device memory, so a replayed hipGraph draws fresh
+ * numbers; with `advance` a one-workgroup launch behind the sampler adds one
+ * to *step (and to *pos, when given) and rewrites *unfinished = rows - (number
+ * of rows with finished != 0): independent of workgroup order.
+ * A row whose `finished` is set emits pad_id and keeps its `length`; another
+ * row's length grows by one and it becomes finished on emitting eos_id.  A
+ * row with no finite candidate emits pad_id.  The token goes to
+ * tokens[row * tok_stride] and, with `history`, to history[row * hist_ld +
+ * (*step - step0)] when that column lies in [0, hist_cols).
+ * ------------------------------------------------------------------------ */
+typedef struct {
+  int rows, vocab;           /* rows >= 1, 1 <= vocab <= 2^24 */
+  int dtype;                 /* MTTS_F32 / MTTS_BF16 (logits) */
+  int top_k;                 /* 0 (or >= vocab): off */
+  int64_t ld;                /* logits row stride (elements), >= vocab */
+  const void* logits;
+  const float* bias;         /* optional (vocab,) or, with bias_ld > 0, (rows, vocab) */
+  int64_t bias_ld;           /* 0: one bias row shared by every row */
+  float temperature;         /* >= 0 */
+  float top_p;               /* (0, 1]; 1: off */
+  const int64_t* seed;       /* device; NULL: 0 */
+  int* step;                 /* device; NULL: 0 (and no advance) */
+  int advance;               /* != 0: *step += 1 (and *pos += 1) after the draw */
+  int step0;                 /* history column = *step - step0 */
+  int* pos;                  /* optional device counter advanced with *step */
+  int64_t* tokens;           /* out */
+  int64_t tok_stride;
+  int64_t* history;          /* optional */
+  int64_t hist_ld;
+  int hist_cols;
+  int eos_id;                /* < 0: none */
+  int pad_id;
+  int reserved_;
+  int* finished;             /* optional (rows,) */
+  int64_t* length;           /* optional (rows,) */
+  int* unfinished;           /* optional: count of rows not yet finished (needs `finished`) */
+} MttsSampleArgs;
+
+int mtts_sample_tokens(const MttsSampleArgs* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -335,3 +335,37 @@ class MambaTTSDecoder(nn.Module):
         with cast_scope(self._gemm_weights(), cd):
             x, pending, new_states = self._run_layers(x, text_hidden, z_style, text_mask, mamba_states)
             return self._tail(x, pending), new_states
+
+    @torch.no_grad()
+    def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, start_token=0,
+                 text_mask=None, ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0,
+                 logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32):
+        """Generate up to `max_new_tokens` codec tokens on the device
+        (mtts/decode.py DecodeEngine.generate): the decode_step loop with the
+        draw (temperature, top-k, top-p, reproducible from `seed`) in the HIP
+        sampler, one hipGraph replay per token under decode_mode "graph", the
+        same step and sampler launched directly under "eager".
+
+        prompt_tokens (B, Tp): continued from; longer than one token it is
+        prefilled through the scan path (equivalent to decode_step on each
+        prompt token in turn: no quant_embed).  Without it generation starts
+        from `start_token` at position 0.
+        logit_bias: fp32 (V,) or (B, V) added to the logits (-inf forbids a
+        token); eos_id: a row that emits it is padded with pad_id from then
+        on, and generation stops once every row has (polled every
+        `check_every` steps).
+
+        Returns tokens (B, n) int64 with n <= max_new_tokens and lengths (B,)
+        int64 (tokens up to and including a row's eos_id)."""
+        if not self.decode_mode:
+            raise RuntimeError("generate runs on the decode engine: set decode_mode to 'graph' or 'eager'")
+        if not (text_hidden.is_cuda and z_style.is_cuda):
+            raise RuntimeError("generate runs on the HIP kernels only (no CPU path)")
+        use_graph = self.decode_mode == "graph"
+        if self._engine is None or self._engine.use_graph != use_graph:
+            self._engine = DecodeEngine(self, use_graph=use_graph)
+        return self._engine.generate(text_hidden, z_style, max_new_tokens, prompt_tokens=prompt_tokens,
+                                     start_token=start_token, text_mask=text_mask, ref_hidden=ref_hidden,
+                                     ref_mask=ref_mask, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
+                                     check_every=check_every)

@@ -17,7 +17,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MTTS_LIB", os.path.join(_HERE, "libmtts.so"))
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 F32, BF16 = 0, 1
 i32, i64, f32, vp = C.c_int, C.c_int64, C.c_float, C.c_void_p
@@ -93,6 +93,14 @@ class DropoutArgs(C.Structure):
     _fields_ = [("n", i64), ("dtype", i32), ("p", f32), ("seed", C.c_uint64), ("x", vp), ("y", vp), ("pre", vp),
                 ("group", i32), ("x_rep", i32), ("x_inner", i32), ("reserved_", i32), ("seed_in", vp),
                 ("seed_out", vp)]
+
+
+class SampleArgs(C.Structure):
+    _fields_ = [("rows", i32), ("vocab", i32), ("dtype", i32), ("top_k", i32), ("ld", i64), ("logits", vp),
+                ("bias", vp), ("bias_ld", i64), ("temperature", f32), ("top_p", f32), ("seed", vp), ("step", vp),
+                ("advance", i32), ("step0", i32), ("pos", vp), ("tokens", vp), ("tok_stride", i64),
+                ("history", vp), ("hist_ld", i64), ("hist_cols", i32), ("eos_id", i32), ("pad_id", i32),
+                ("reserved_", i32), ("finished", vp), ("length", vp), ("unfinished", vp)]
 
 
 class RowMap(C.Structure):
@@ -202,6 +210,7 @@ _SIGS = {
     "mtts_length_regulate_fwd": ([vp, i32, i32, i32, i32, i64, i64, vp, i64, i32, vp, i64, i64, vp], i32),
     "mtts_length_regulate_bwd": ([vp, i32, i32, i32, i32, i64, i64, vp, i64, i32, vp, i64, i64, vp], i32),
     "mtts_dropout": ([C.POINTER(DropoutArgs), vp], i32),
+    "mtts_sample_tokens": ([C.POINTER(SampleArgs), vp], i32),
 }
 
 _lib = None

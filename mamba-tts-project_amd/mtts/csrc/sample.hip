@@ -1,0 +1,291 @@
+// Token sampler in HIP: the end of an autoregressive decode step
+// (mamba_decoder.py:188-256 returns logits and leaves the draw to the caller).
+// One launch turns (rows, V) logits into one token per row: temperature,
+// top-k, nucleus (top-p) and a Gumbel-max draw from a counter-based hash, so
+// a float64 reference can reproduce every token (include/mtts.h, ABI 15).
+//
+// One workgroup per row: a single wave for V <= 256 (every reduction stays in
+// the wave: no LDS round trip, no barrier), 4 waves for longer rows, so that a
+// thread walks at most 4 entries per pass up to V = 1024 (one wave over 1024
+// entries measured slower: 16 dependent LDS reads per pass and 16 Gumbel
+// draws per lane, +99 us per token against +39).  A thread owns the entries
+// v = tid + threads * j in every pass, so the row staged in LDS (V <= 4096;
+// longer rows are re-read from L2) is per-thread storage and needs no barrier
+// of its own.
+//   * order-free selection: both filters are thresholds on the logit.  With
+//     key(x) the monotone uint32 image of a float, top-k keeps key >= K, K the
+//     smallest key with #{key_w > K} < top_k, and top-p keeps key >= K2, K2
+//     the smallest key with sum_{key_w > K2} e_w < top_p * Z: two bisections
+//     over the key space (<= 32 block reductions each, one barrier per
+//     reduction on alternating LDS slots).  Ties share a key, so they stay or
+//     go together, as the definition asks.
+//   * the draw: u = ((h >> 40) + 0.5) * 2^-24 needs 25 significant bits above
+//     1/2; there -log(u) is taken as -log1p(-(1 - u)) with 1 - u exact in
+//     fp32, so the Gumbel noise is good to a few ulp over the whole range
+//     (precise logf / log1pf, not v_log_f32).
+//   * (score, index) pairs reduce as one uint64 max: key(score) << 32 | ~index
+//     gives the largest score and, on ties, the lowest index.
+// The step counter is read by every workgroup and advanced by a one-workgroup
+// launch behind the sampler (which also recounts the unfinished rows), so
+// nothing depends on the order in which workgroups run and there are no
+// atomics.
+#include "common.h"
+
+#include <math.h>
+
+namespace mtts {
+namespace {
+
+constexpr int kSampleThreads = 256;
+constexpr int kSampleCache = 4096;   // row entries staged in LDS (4-wave form)
+constexpr int kSampleWaveV = 256;    // longest row of the one-wave form (all of it staged)
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64's finalizer (as dropout.hip)
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// monotone image of a float: a < b  <=>  fkey(a) < fkey(b) (no NaN; -0 was folded into +0)
+__device__ __forceinline__ uint32_t fkey(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float unkey(uint32_t k) {
+  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
+__device__ __forceinline__ uint64_t bits_of(uint64_t v) { return v; }
+__device__ __forceinline__ uint64_t bits_of(uint32_t v) { return v; }
+__device__ __forceinline__ uint64_t bits_of(float v) { return __float_as_uint(v); }
+__device__ __forceinline__ void from_bits(uint64_t b, uint64_t& v) { v = b; }
+__device__ __forceinline__ void from_bits(uint64_t b, uint32_t& v) { v = (uint32_t)b; }
+__device__ __forceinline__ void from_bits(uint64_t b, float& v) { v = __uint_as_float((uint32_t)b); }
+
+struct OpSum {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct OpMax {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+
+// Reduction over the workgroup's NW (1 or 4) waves in a fixed order (the same value in
+// every thread, the same bits in every run).  One barrier per call: calls
+// alternate between two slot rows, and a wave can only write a row again
+// after every wave has passed the barrier of the call in between.
+template <int NW, typename T, typename Op>
+__device__ __forceinline__ T block_red(T v, Op op, uint64_t (*slots)[4], int& phase) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = op(v, __shfl_xor(v, o));
+  if constexpr (NW == 1) return v;
+  uint64_t* s = slots[phase];
+  phase ^= 1;
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = bits_of(v);
+  block_sync();
+  T r0, r1, r2, r3;
+  from_bits(s[0], r0); from_bits(s[1], r1); from_bits(s[2], r2); from_bits(s[3], r3);
+  return op(op(r0, r1), op(r2, r3));
+}
+
+// The bisections' sums (32 + 32 of them per row): the wave part on DPP /
+// permlane moves (common.h wave_sum) instead of six ds_bpermute round trips.
+// A count goes through as a float: exact below 2^24, the vocabulary's bound.
+template <int NW>
+__device__ __forceinline__ float block_sum(float v, uint64_t (*slots)[4], int& phase) {
+  v = wave_sum(v);
+  if constexpr (NW == 1) return v;
+  uint64_t* s = slots[phase];
+  phase ^= 1;
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = bits_of(v);
+  block_sync();
+  float r0, r1, r2, r3;
+  from_bits(s[0], r0); from_bits(s[1], r1); from_bits(s[2], r2); from_bits(s[3], r3);
+  return (r0 + r1) + (r2 + r3);
+}
+
+// -log(-log(u)), u = (n + 0.5) * 2^-24 for the 24-bit n
+__device__ __forceinline__ float gumbel(uint32_t n) {
+  float a;
+  if (n < (1u << 23)) {
+    a = -logf((float)(2 * n + 1) * 0x1p-25f);                       // u <= 1/2: exact in fp32
+  } else {
+    a = -log1pf(-((float)(2 * ((1u << 24) - 1 - n) + 1) * 0x1p-25f));   // 1 - u exact
+  }
+  return -logf(a);
+}
+
+struct SampleParams {
+  MttsSampleArgs a;
+};
+
+template <typename T, int NW>
+__global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm) {
+  constexpr int kThreads = NW * 64;
+  constexpr int kCache = NW == 1 ? kSampleWaveV : kSampleCache;
+  const MttsSampleArgs& p = prm.a;
+  __shared__ float xs[kCache];
+  __shared__ float es[kCache];
+  __shared__ uint64_t slots[2][4];
+  int phase = 0;
+  const int row = blockIdx.x, tid = threadIdx.x, V = p.vocab;
+  const int step = p.step ? *p.step : 0;
+  const int col = step - p.step0;
+  int64_t* const hist = (p.history && col >= 0 && col < p.hist_cols) ? p.history + (int64_t)row * p.hist_ld + col
+                                                                     : nullptr;
+  int64_t* const tok_out = p.tokens + (int64_t)row * p.tok_stride;
+  if (p.finished && p.finished[row] != 0) {   // past its end of sequence: pad, length frozen
+    if (tid == 0) {
+      *tok_out = p.pad_id;
+      if (hist) *hist = p.pad_id;
+    }
+    return;
+  }
+  const T* __restrict__ lg = reinterpret_cast<const T*>(p.logits) + (int64_t)row * p.ld;
+  const float* __restrict__ bias = p.bias ? p.bias + (int64_t)row * p.bias_ld : nullptr;
+  const bool cached = V <= kCache;
+  auto load = [&](int v) {
+    float x = ldf(lg + v);
+    if (bias) x += bias[v];
+    if (!(x == x)) x = -INFINITY;   // NaN counts as -inf
+    if (x == 0.f) x = 0.f;          // -0 and +0 tie: one key
+    return x;
+  };
+  auto X = [&](int v) { return cached ? xs[v] : load(v); };
+
+  // row maximum and its lowest index
+  uint64_t best = 0;
+  for (int v = tid; v < V; v += kThreads) {
+    const float x = load(v);
+    if (cached) xs[v] = x;
+    const uint64_t c = ((uint64_t)fkey(x) << 32) | (uint32_t)~(uint32_t)v;
+    best = c > best ? c : best;
+  }
+  best = block_red<NW>(best, OpMax(), slots, phase);
+  const uint32_t kmax = (uint32_t)(best >> 32);
+  const float m = unkey(kmax);
+  int64_t token = (int64_t)(uint32_t)~(uint32_t)best;
+  if (m == -INFINITY) {
+    token = p.pad_id;               // no finite candidate
+  } else if (p.temperature > 0.f && m < INFINITY) {
+    const float T_ = p.temperature;
+    const float invT = 1.f / T_;
+    uint32_t K = 0;
+    if (p.top_k > 0 && p.top_k < V) {
+      const uint32_t k = (uint32_t)p.top_k;
+      uint32_t lo = 0, hi = kmax;
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        uint32_t cnt = 0;
+#pragma unroll 4
+        for (int v = tid; v < V; v += kThreads) cnt += fkey(X(v)) > mid ? 1u : 0u;
+        if ((uint32_t)block_sum<NW>((float)cnt, slots, phase) < k) hi = mid; else lo = mid + 1;
+      }
+      K = lo;
+    }
+    if (p.top_p < 1.f) {
+      // e_v = exp((x_v - m) / T) over the top-k survivors (0 elsewhere; exp(-inf) = 0)
+      auto E = [&](int v, float x) { return fkey(x) >= K ? expf((x - m) * invT) : 0.f; };
+      float z = 0.f;
+      for (int v = tid; v < V; v += kThreads) {
+        const float e = E(v, X(v));
+        if (cached) es[v] = e;
+        z += e;
+      }
+      z = block_sum<NW>(z, slots, phase);
+      const float target = p.top_p * z;
+      uint32_t lo = K, hi = kmax;
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        float s = 0.f;
+#pragma unroll 4
+        for (int v = tid; v < V; v += kThreads) {
+          const float x = X(v);
+          if (fkey(x) > mid) s += cached ? es[v] : E(v, x);
+        }
+        s = block_sum<NW>(s, slots, phase);
+        if (s < target) hi = mid; else lo = mid + 1;
+      }
+      K = lo;
+    }
+    // Gumbel-max draw over the kept set
+    const uint64_t seed = p.seed ? (uint64_t)*p.seed : 0ull;
+    const uint64_t c0 = ((uint64_t)(int64_t)step * (uint64_t)p.rows + (uint64_t)row) * (uint64_t)V;
+    uint64_t pick = 0;
+    for (int v = tid; v < V; v += kThreads) {
+      const float x = X(v);
+      if (x > -INFINITY && fkey(x) >= K) {
+        const uint64_t h = mix64(seed + (c0 + (uint64_t)v) * 0x9E3779B97F4A7C15ull);
+        const float score = x / T_ + gumbel((uint32_t)(h >> 40));
+        const uint64_t c = ((uint64_t)fkey(score) << 32) | (uint32_t)~(uint32_t)v;
+        pick = c > pick ? c : pick;
+      }
+    }
+    pick = block_red<NW>(pick, OpMax(), slots, phase);
+    token = (int64_t)(uint32_t)~(uint32_t)pick;   // the row maximum is always kept: pick != 0
+  }
+  if (tid == 0) {
+    *tok_out = token;
+    if (hist) *hist = token;
+    if (p.length) p.length[row] += 1;
+    if (p.finished && p.eos_id >= 0 && token == p.eos_id) p.finished[row] = 1;
+  }
+}
+
+// Behind the sampler: count the unfinished rows and advance the counters.
+__global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* step, int* pos, const int* finished,
+                                                                        int rows, int* unfinished, int advance) {
+  __shared__ uint64_t slots[2][4];
+  int phase = 0;
+  uint32_t done = 0;
+  if (unfinished) {
+    for (int r = threadIdx.x; r < rows; r += kSampleThreads) done += finished[r] != 0 ? 1u : 0u;
+    done = block_red<4>(done, OpSum(), slots, phase);
+  }
+  if (threadIdx.x == 0) {
+    if (unfinished) *unfinished = rows - (int)done;
+    if (advance) {
+      if (step) *step += 1;
+      if (pos) *pos += 1;
+    }
+  }
+}
+
+}  // namespace
+}  // namespace mtts
+
+using namespace mtts;
+
+extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
+  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens: null pointer");
+  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens: dtype must be f32 or bf16");
+  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24), "sample_tokens: rows=%d vocab=%d out of range",
+             a->rows, a->vocab);
+  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
+             "sample_tokens: row stride below vocab");
+  MTTS_CHECK(a->temperature >= 0.f, "sample_tokens: temperature=%f must be >= 0", (double)a->temperature);
+  MTTS_CHECK(a->top_k >= 0, "sample_tokens: top_k=%d must be >= 0", a->top_k);
+  MTTS_CHECK(a->top_p > 0.f && a->top_p <= 1.f, "sample_tokens: top_p=%f must be in (0, 1]", (double)a->top_p);
+  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
+             "sample_tokens: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
+  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols), "sample_tokens: bad history shape");
+  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens: unfinished needs finished");
+  MTTS_CHECK(!a->advance || a->step, "sample_tokens: advance needs step");
+  hipStream_t st = (hipStream_t)stream;
+  SampleParams prm;
+  prm.a = *a;
+  const bool f32 = a->dtype == MTTS_F32;
+  if (a->vocab <= kSampleWaveV) {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1>), dim3(a->rows), dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1>), dim3(a->rows), dim3(64), 0, st, prm);
+  } else {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 4>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 4>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+  }
+  MTTS_LAUNCH_CHECK("sample_tokens");
+  if (a->advance || a->unfinished) {
+    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
+                       a->rows, a->unfinished, a->advance);
+    MTTS_LAUNCH_CHECK("sample_tokens (advance)");
+  }
+  return MTTS_OK;
+}

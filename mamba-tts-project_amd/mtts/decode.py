@@ -21,6 +21,10 @@ Engine path (inference only: torch.no_grad, HIP tensors):
   * dt_proj fused into the selective state update (B / C read in place);
   * optional hipGraph capture of the whole step (static token / position /
     state buffers): replay costs one launch instead of ~25 per layer.
+  * generate(): the loop around the step on the device -- one hipGraph of
+    step + token sampler (csrc/sample.hip) replayed per token, the token,
+    step and position counters never leaving HBM; a prompt prefilled through
+    the scan path.
 Numerics are those of the eager module path (tests/test_gpu_modules.py).
 Call `reset()` after modifying weights in place between decode steps.
 """
@@ -32,9 +36,9 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
-from .embed import _err_flag
+from .embed import _err_flag, embed_sum
 from .attn_kernels import attention, attention_decode_packed, attention_decode_qproj_packed
-from .linear import cast_weight
+from .linear import cast_scope, cast_weight
 
 
 def _same_ctx(refs, versions, tensors):
@@ -106,6 +110,8 @@ class DecodeEngine:
         self.ctx_versions = None
         self.ctx = None
         self.graph = None
+        self.gen_graphs = {}
+        self.gen = None
         self.states = None
         if flagged:
             raise IndexError("decode_step: last_token id out of range of token_embed (index out of range in self)")
@@ -382,29 +388,29 @@ class DecodeEngine:
         self._err_host.copy_(_err_flag(dev), non_blocking=True)
         self._err_ev.record()
 
-    # -- public ----------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, last_token, text_hidden, z_style, mamba_states, step_index, text_mask=None, ref_hidden=None,
-             ref_mask=None):
+    def _prepare(self, conds, tok_shape, dev):
+        """Conditioning context (rebuilt when `conds`, the compute dtype or the
+        token shape changed; every graph goes with it) and the static state /
+        token / position buffers."""
         m = self.m
-        self._check_token_flag(last_token.device)
+        text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
         cd = m._cd()
-        conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
-        key = (cd, tuple(last_token.shape))
+        key = (cd, tok_shape)
+        B = tok_shape[0]
         if key != self.ctx_key or not _same_ctx(self.ctx_refs, self.ctx_versions, conds):
             self.ctx = self._build_ctx(text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd)
             self.ctx_key = key
             self.ctx_refs = conds                  # strong references (see _same_ctx)
             self.ctx_versions = tuple(None if t is None else t._version for t in conds)
-            self.fused = self._fused_ok(cd, last_token.shape[0])
+            self.fused = self._fused_ok(cd, B)
             if self.fused and self.OPTIONS["packed"]:
                 self._pack_ctx()
             self.xpk = self.fused and self._xpk_ok()
-            self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(last_token.shape[0])
+            self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(B)
             self.graph = None
+            self.gen_graphs = {}
+            self.gen = None
             self.states = None
-        B = last_token.shape[0]
-        dev = last_token.device
         if self.states is None:
             self.states = []
             for l in m.layers:
@@ -414,6 +420,16 @@ class DecodeEngine:
             self.tok_buf = torch.zeros(B, 1, dtype=torch.long, device=dev)
             self.pos_buf = torch.zeros(1, dtype=torch.long, device=dev)
             self.pos32 = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    # -- public ----------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, last_token, text_hidden, z_style, mamba_states, step_index, text_mask=None, ref_hidden=None,
+             ref_mask=None):
+        m = self.m
+        self._check_token_flag(last_token.device)
+        B = last_token.shape[0]
+        dev = last_token.device
+        self._prepare((text_hidden, z_style, text_mask, ref_hidden, ref_mask), tuple(last_token.shape), dev)
         # adopt the caller's states (None = start of sequence)
         for i, st in enumerate(self.states):
             given = None if mamba_states is None else mamba_states[i]
@@ -458,3 +474,183 @@ class DecodeEngine:
         if self.fused:
             self._post_token_flag(dev)
         return self.out_buf.clone(), list(self.states)
+
+    # -- generation ------------------------------------------------------------
+    def _gen_buffers(self, B, V, dev):
+        """Device-resident generation state, made once per context (before any
+        capture): seed / step counters, the token history, end-of-sequence
+        bookkeeping, the logit bias and pinned slots for the early-stop polls."""
+        if self.gen is None:
+            cap = self.m.pos_embed.num_embeddings
+            self.gen = dict(
+                seed=torch.zeros(1, dtype=torch.int64, device=dev), step=torch.zeros(1, dtype=torch.int32, device=dev),
+                hist=torch.zeros(B, cap, dtype=torch.int64, device=dev),
+                finished=torch.zeros(B, dtype=torch.int32, device=dev),
+                length=torch.zeros(B, dtype=torch.int64, device=dev),
+                unfinished=torch.zeros(1, dtype=torch.int32, device=dev),
+                bias=torch.zeros(B, V, dtype=torch.float32, device=dev),
+                host=torch.zeros(cap, dtype=torch.int32, pin_memory=True))
+        return self.gen
+
+    def _prefill(self, prompt, conds):
+        """The whole prompt through the parallel (scan) path: one embed_sum
+        with a zero quantizer row (decode_step adds no quant_embed,
+        mamba_decoder.py:217-221), the layer stack from empty states, the head
+        on the last position.  The per-layer (conv_state, ssm_state) it returns
+        become the engine's states; returns the last position's logits (B, V)."""
+        m, c = self.m, self.ctx
+        text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
+        cd = c["cd"]
+        B, Tp = prompt.shape
+        th = text_hidden.to(cd)
+        th, tm = m._concat_ref(th, text_mask, ref_hidden, ref_mask, B, th.device)
+        qid = torch.zeros(Tp, dtype=torch.long, device=prompt.device)
+        x = embed_sum(prompt, qid, m.token_embed.weight, c["q0_w"], m.pos_embed.weight, cd)
+        with cast_scope(m._gemm_weights(), cd):
+            x, pending, new_states = m._run_layers(x, th, z_style, tm, None)
+            logits = m._tail(x[:, -1:].contiguous(), None if pending is None else pending[:, -1:].contiguous())
+        for (cs, ss), (ncs, nss) in zip(self.states, new_states):
+            cs.copy_(ncs)
+            ss.copy_(nss)
+        return logits[:, 0]
+
+    @torch.no_grad()
+    def generate(self, text_hidden, z_style, max_new_tokens, prompt_tokens=None, start_token=0, text_mask=None,
+                 ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, eos_id=None,
+                 pad_id=0, seed=0, check_every=32):
+        """Autoregressive generation on the device: each new token is one
+        replay of a hipGraph holding the decode step and the sampler
+        (csrc/sample.hip), which writes the token buffer the next step embeds,
+        the history column and the end-of-sequence bookkeeping, and advances
+        the step / position counters -- no per-token copy, fill, clone or
+        error-flag read on the host.  A prompt longer than one token is
+        prefilled through the scan path (_prefill) and its last logits feed
+        the first draw; prompt tokens sit at positions 0..Tp-1, new token i is
+        drawn from the logits at position Tp-1+i and fed at Tp+i.
+
+        The seed lives in device memory (a new seed replays the same graph);
+        temperature / top_k / top_p / eos_id / pad_id key the graph cache.
+        With eos_id, every `check_every` steps the unfinished-row count is
+        copied to pinned memory without blocking and the previous poll is
+        waited for (so the host runs at most two polls ahead of the GPU);
+        generation stops once a poll reads 0.  The engine's state buffers are
+        reused: a decode_step sequence in flight on this engine does not
+        survive a generate call (a following one, from step 0, does).
+
+        Returns tokens (B, n) int64, n <= max_new_tokens, and lengths (B,)."""
+        m = self.m
+        V = m.head.weight.shape[0]
+        B = text_hidden.shape[0]
+        dev = text_hidden.device
+        n_new = int(max_new_tokens)
+        if n_new < 1 or int(check_every) < 1:
+            raise ValueError("generate: max_new_tokens and check_every must be >= 1")
+        if prompt_tokens is not None and (prompt_tokens.dim() != 2 or prompt_tokens.shape[0] != B
+                                          or prompt_tokens.shape[1] < 1):
+            raise ValueError("generate: prompt_tokens must be (B, Tp) with Tp >= 1")
+        Tp = 1 if prompt_tokens is None else prompt_tokens.shape[1]
+        if Tp + n_new - 1 > m.pos_embed.num_embeddings:
+            raise IndexError(f"generate: {Tp} prompt + {n_new} new tokens need positions beyond pos_embed "
+                             f"({m.pos_embed.num_embeddings}) (index out of range in self)")
+        if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
+            raise ValueError(f"generate: pad_id / eos_id outside the vocabulary of {V}")
+        if not 0 < top_p <= 1:
+            raise ValueError("generate: top_p must be in (0, 1]")
+        if temperature < 0 or top_k < 0:
+            raise ValueError("generate: temperature and top_k must be >= 0")
+        if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (B, V)):
+            raise ValueError("generate: logit_bias must be (V,) or (B, V)")
+        n_tok = m.token_embed.num_embeddings
+        if prompt_tokens is None:
+            if not 0 <= int(start_token) < n_tok:
+                raise IndexError("generate: start_token out of range of token_embed (index out of range in self)")
+        elif int(prompt_tokens.min()) < 0 or int(prompt_tokens.max()) >= n_tok:
+            raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
+        self.check_errors()                         # a flag left by earlier decode_steps is theirs
+        conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
+        self._prepare(conds, (B, 1), dev)
+        g = self._gen_buffers(B, V, dev)
+        stepfn = self._step_rows if self.fused else self._step
+        eos = None if eos_id is None else int(eos_id)
+
+        def draw(logits):
+            ops.sample_tokens(logits, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                              logit_bias=g["bias"], seed=g["seed"], step=g["step"], advance=True, out=self.tok_buf,
+                              history=g["hist"], eos_id=eos, pad_id=int(pad_id), finished=g["finished"],
+                              length=g["length"], unfinished=g["unfinished"],
+                              pos=self.pos32 if self.fused else None)
+            if not self.fused:
+                self.pos_buf.add_(1)
+
+        def body():
+            draw(stepfn(self.tok_buf, self.pos_buf, self.states)[:, 0])
+
+        def rewind():
+            for t in (self.tok_buf, self.pos_buf, self.pos32, g["step"], g["finished"], g["length"]):
+                t.zero_()
+            for cs, ss in self.states:
+                cs.zero_()
+                ss.zero_()
+
+        run = body
+        if self.use_graph:
+            key = (float(temperature), int(top_k), float(top_p), eos, int(pad_id))
+            gr = self.gen_graphs.get(key)
+            if gr is None:
+                g["bias"].zero_()
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(2):  # warm up (allocator, library handles, lazily made workspaces)
+                        rewind()
+                        body()
+                torch.cuda.current_stream().wait_stream(s)
+                rewind()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr):
+                    body()
+                self.gen_graphs[key] = gr
+            run = gr.replay
+        # this call's state
+        rewind()
+        g["seed"].fill_((int(seed) + (1 << 63)) % (1 << 64) - (1 << 63))
+        g["unfinished"].fill_(B)
+        if logit_bias is None:
+            g["bias"].zero_()
+        else:
+            g["bias"].copy_(logit_bias.to(torch.float32).expand(B, V))
+        issued = 0
+        if Tp > 1:
+            logits0 = self._prefill(prompt_tokens.long(), conds)
+            self.prefill_logits = logits0
+            self.pos32.fill_(Tp - 1)
+            self.pos_buf.fill_(Tp - 1)
+            draw(logits0)                           # token 0 from the prompt's last logits; pos -> Tp
+            issued = 1
+        elif prompt_tokens is not None:
+            self.tok_buf.copy_(prompt_tokens)
+        else:
+            self.tok_buf.fill_(int(start_token))
+        polls, prev = 0, None
+        while issued < n_new:
+            run()
+            issued += 1
+            if eos is not None and issued % int(check_every) == 0 and issued < n_new:
+                g["host"][polls:polls + 1].copy_(g["unfinished"], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                if prev is not None:
+                    prev.synchronize()
+                    if int(g["host"][polls - 1]) == 0:
+                        break
+                prev = ev
+                polls += 1
+        if self.fused:
+            self._post_token_flag(dev)
+        torch.cuda.current_stream().synchronize()
+        self.check_errors()
+        lengths = g["length"].clone()
+        n = issued
+        if eos is not None and int(g["unfinished"].item()) == 0:
+            n = int(lengths.max())                  # trimmed at the step where every row had finished
+        return g["hist"][:, :n].clone(), lengths

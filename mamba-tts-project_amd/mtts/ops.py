@@ -788,3 +788,87 @@ def gemm_rows(x, weight, bias=None, act=None, conv=None, ln=None, res=None, pack
         a.kgroups, a.splitk_slab, a.splitk_count = kg, slab.data_ptr(), cnt.data_ptr()
     L.call("mtts_gemm_rows", a)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# token sampler (csrc/sample.hip)
+# ---------------------------------------------------------------------------
+def _dev_scalar(v, dtype, dev, name):
+    """An int, or a one-element device tensor of `dtype` (read by the kernel
+    at run time, so a captured launch sees what the buffer holds at replay)."""
+    if isinstance(v, torch.Tensor):
+        if v.dtype != dtype or v.numel() != 1 or v.device != dev:
+            raise ValueError(f"sample_tokens: {name} must be an int or a one-element {dtype} tensor on {dev}")
+        return v
+    return torch.full((1,), int(v), dtype=dtype, device=dev)
+
+
+def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, seed, step, advance=False,
+                  out=None, history=None, step0=0, eos_id=None, pad_id=0, finished=None, length=None,
+                  unfinished=None, pos=None):
+    """One token per row of `logits` (rows, V) fp32 / bf16 (unit column
+    stride, any row stride) in one HIP launch: x = logits + logit_bias,
+    greedy for temperature == 0, else top-k, then top-p on softmax(x / T),
+    then a Gumbel-max draw from a counter-based hash of (seed, step, row, v)
+    (include/mtts.h, MttsSampleArgs, has the exact definition).
+
+    logit_bias: fp32 (V,) or (rows, V); -inf forbids a token.
+    seed (int64) / step (int32): ints, or one-element device tensors read at
+    run time -- capture the call once and every replay draws from what the
+    buffers hold; advance=True adds one to `step` (and to the int32 device
+    counter `pos`, when given) behind the draw.
+    out: int64 destination, any view with one element per row (default: a new
+    (rows,) tensor).  history (rows, n) int64: column step - step0 also
+    receives the token.  finished (rows,) int32 / length (rows,) int64 /
+    unfinished (1,) int32: end-of-sequence bookkeeping -- a finished row emits
+    pad_id and keeps its length, a row becomes finished on emitting eos_id,
+    and `unfinished` is rewritten with the number of rows still running.
+    Returns the tokens."""
+    _check_cuda(logits, logit_bias, out, history, finished, length, unfinished, pos)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("sample_tokens: logits must be (rows, V) with unit column stride")
+    rows, V = logits.shape
+    dev = logits.device
+    if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
+        raise ValueError("sample_tokens: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
+    if not 0 <= pad_id < V or (eos_id is not None and not 0 <= eos_id < V):
+        raise ValueError("sample_tokens: pad_id / eos_id outside the vocabulary")
+    a = L.SampleArgs()
+    a.rows, a.vocab, a.dtype, a.top_k = rows, V, L.dtype_code(logits), int(top_k)
+    a.ld, a.logits = logits.stride(0) if rows > 1 else max(logits.stride(0), V), logits.data_ptr()
+    if logit_bias is not None:
+        if (logit_bias.dtype != torch.float32 or logit_bias.stride(-1) != 1
+                or tuple(logit_bias.shape) not in ((V,), (rows, V))):
+            raise ValueError("sample_tokens: logit_bias must be fp32 (V,) or (rows, V) with unit column stride")
+        a.bias = logit_bias.data_ptr()
+        a.bias_ld = logit_bias.stride(0) if logit_bias.dim() == 2 and rows > 1 else 0
+    a.temperature, a.top_p = float(temperature), float(top_p)
+    seed_t = _dev_scalar(seed, torch.int64, dev, "seed")
+    step_t = _dev_scalar(step, torch.int32, dev, "step")
+    a.seed, a.step, a.advance, a.step0 = seed_t.data_ptr(), step_t.data_ptr(), int(bool(advance)), int(step0)
+    if pos is not None:
+        if pos.dtype != torch.int32 or pos.numel() != 1:
+            raise ValueError("sample_tokens: pos must be a one-element int32 tensor")
+        a.pos = pos.data_ptr()
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=dev)
+    if out.dtype != torch.int64 or out.numel() != rows:
+        raise ValueError("sample_tokens: out must hold one int64 per row")
+    flat = out.reshape(-1) if out.dim() != 1 else out
+    if flat.data_ptr() != out.data_ptr():
+        raise ValueError("sample_tokens: out must be viewable as one strided vector")
+    a.tokens, a.tok_stride = out.data_ptr(), flat.stride(0) if rows > 1 else 1
+    if history is not None:
+        if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or history.stride(1) != 1:
+            raise ValueError("sample_tokens: history must be (rows, n) int64 with unit column stride")
+        a.history, a.hist_ld, a.hist_cols = history.data_ptr(), max(history.stride(0), history.shape[1]), history.shape[1]
+    a.eos_id, a.pad_id = -1 if eos_id is None else int(eos_id), int(pad_id)
+    for t, dt, n, name in ((finished, torch.int32, rows, "finished"), (length, torch.int64, rows, "length"),
+                           (unfinished, torch.int32, 1, "unfinished")):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of {n} element(s)")
+    if unfinished is not None and finished is None:
+        raise ValueError("sample_tokens: unfinished needs finished")
+    a.finished, a.length, a.unfinished = L.ptr(finished), L.ptr(length), L.ptr(unfinished)
+    L.call("mtts_sample_tokens", a)
+    return out
