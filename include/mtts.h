@@ -32,6 +32,12 @@
 extern "C" {
 #endif
 
+/* 15 also covers the ragged-batch additions, which are purely additive:
+ * `seqlens` appended to MttsScanFwdArgs and MttsConvFwdArgs (NULL = the old
+ * behaviour), MttsSampleArgs.reserved_ named pos_rows (0 = the old behaviour,
+ * same offset and size) and one new symbol, mtts_embed_sum_at.  A caller
+ * built against the earlier header must zero the appended fields; a binding
+ * that needs the additions checks that mtts_embed_sum_at resolves. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -86,6 +92,14 @@ int mtts_get_override(int key);
  * ckpt (optional)  : (B, ceil(L/ckpt_chunk), D, N) fp32 — h at the START of
  *                    every chunk of `ckpt_chunk` steps (the backward's
  *                    restart points; upstream saves `x` chunk states too).
+ * seqlens (optional): device int32 (B): a ragged, right-padded batch.  Row b
+ *                    runs len_b = clamp(seqlens[b], 0, L) steps: last_state[b]
+ *                    is h after step len_b - 1 (h0[b] or 0 when len_b == 0),
+ *                    out[b, t < len_b] is what the call gives on the row cut
+ *                    to len_b steps, out[b, t >= len_b] is not written and no
+ *                    input at t >= len_b is read.  Inference only: with ckpt,
+ *                    or in the backward, it is MTTS_EINVAL.  NULL: every row
+ *                    runs L steps.
  * ------------------------------------------------------------------------ */
 typedef struct {
   int batch, dim, seqlen, dstate;
@@ -114,6 +128,7 @@ typedef struct {
   float* last_state;       /* optional */
   float* ckpt;             /* optional */
   void* workspace;         /* mtts_selective_scan_fwd_workspace() bytes */
+  const int* seqlens;      /* optional device (B): per-row valid length */
 } MttsScanFwdArgs;
 
 /* Scratch for the sequence-segment pass (0 bytes when B*D fills the chip). */
@@ -156,6 +171,10 @@ int mtts_selective_scan_bwd(const MttsScanBwdArgs* a, void* stream);
  * where xx is x preceded by the K pre-conv inputs in conv_state_in
  * (B, D, K) (zeros when NULL).  conv_state_out (B, D, K), optional, receives
  * the last K inputs of [conv_state_in ‖ x] (mamba-ssm prefill semantics).
+ * With seqlens (device int32 (B), optional) conv_state_out[b] is the last K
+ * inputs of [conv_state_in[b] ‖ x[b, :len_b]], len_b = clamp(seqlens[b], 0,
+ * L): the state a ragged, right-padded row leaves behind.  `out` does not
+ * depend on it; the backward rejects it (MTTS_EINVAL).
  * ------------------------------------------------------------------------ */
 typedef struct {
   int batch, dim, seqlen, width;
@@ -168,6 +187,7 @@ typedef struct {
   const float* conv_state_in;     /* optional (B, D, K) */
   void* out;
   float* conv_state_out;          /* optional (B, D, K) */
+  const int* seqlens;             /* optional device (B): per-row valid length (conv_state_out only) */
 } MttsConvFwdArgs;
 
 int mtts_causal_conv1d_fwd(const MttsConvFwdArgs* a, void* stream);
@@ -465,6 +485,16 @@ int mtts_clip_adam(const MttsAdamTensor* tensors, int ntensors, int64_t total_ch
 int mtts_embed_sum(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
                    const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d, int vocab,
                    void* out, int dtype, int64_t out_bs, int* err_flag, void* stream);
+/* The same sum with per-row positions (a ragged batch decodes every row at
+ * its own position): pos_ids[b * pos_bs + l], pos_bs = 0 sharing one (L) row
+ * as above.  A position outside [0, n_pos) (n_pos > 0: the rows of pos_w, or
+ * a tighter bound) is handled like a token outside the vocabulary:
+ * *err_flag = 1, the output row is written as zeros and no table is read out
+ * of bounds.  mtts_embed_sum is this call with pos_bs = 0 and unchecked
+ * positions. */
+int mtts_embed_sum_at(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
+                      const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d, int vocab,
+                      void* out, int dtype, int64_t out_bs, int* err_flag, int64_t pos_bs, int n_pos, void* stream);
 
 /* Gradient of a small embedding table (ABI 14; csrc/regulate.hip): the
  * token-embedding backward of mamba_decoder.py:167 (token_embed) and
@@ -829,7 +859,7 @@ typedef struct {
   int hist_cols;
   int eos_id;                /* < 0: none */
   int pad_id;
-  int reserved_;
+  int pos_rows;              /* 0: `pos` is one counter; n > 0: pos[0..n) all advance (per-row positions) */
   int* finished;             /* optional (rows,) */
   int64_t* length;           /* optional (rows,) */
   int* unfinished;           /* optional: count of rows not yet finished (needs `finished`) */

@@ -94,7 +94,7 @@ class MambaTTSDecoderLayer(nn.Module):
         return x + ff_out, new_state                                          # :88-89
 
     def forward_fused(self, x, pending, text_hidden, z_style, text_mask=None, mamba_state=None, kpm=None, gb=None,
-                      ff_slot=True, kv=None):
+                      ff_slot=True, kv=None, seq_lens=None):
         """Same math as forward(); the input residual `x + pending` and the
         output residual `x + ff_out` are left to the neighbouring fused
         residual+LayerNorm kernels.  `gb` (B, 2d): this layer's
@@ -105,6 +105,8 @@ class MambaTTSDecoderLayer(nn.Module):
         slot attached to it as `_mtts_dbias_slot`).
         `kv`: this layer's K/V projection of text_hidden when the decoder
         ran all layers' at once (mtts.attention.kv_all).
+        `seq_lens` (B,): x is a ragged, right-padded batch (inference only);
+        new_state is then each row's state after its own length.
         Returns (x, ff_out, new_state)."""
         T = x.shape[1]
         # 1) (x += pending) ; h = norm_mamba(x) ; Mamba   (mamba_decoder.py:59-64)
@@ -113,7 +115,8 @@ class MambaTTSDecoderLayer(nn.Module):
                                colsum_slot=getattr(pending, "_mtts_dbias_slot", None))
         if pending is not None:
             x = xs
-        h_mamba, new_state = self.mamba(h, mamba_state)
+        h_mamba, new_state = (self.mamba(h, mamba_state) if seq_lens is None
+                              else self.mamba(h, mamba_state, seq_lens=seq_lens))
 
         # 2) x = x + h_mamba ; h = norm_cross(x)   (fused, :64-67)
         h, x = ops.layer_norm(h_mamba, self.norm_cross.weight, self.norm_cross.bias, self.norm_cross.eps, res=x)
@@ -227,7 +230,7 @@ class MambaTTSDecoder(nn.Module):
         params = [t for m in lins for t in (m.weight, m.bias)]
         return StyleMLPAll.apply(z_style.to(w0.dtype), cd, *params)
 
-    def _run_layers(self, x, text_hidden, z_style, text_mask, states):
+    def _run_layers(self, x, text_hidden, z_style, text_mask, states, seq_lens=None):
         pending = None
         new_states = []
         kpm = None if text_mask is None else ~text_mask                     # :68-70 (sic), once for all layers
@@ -240,7 +243,7 @@ class MambaTTSDecoder(nn.Module):
             x, pending, st = layer.forward_fused(x, pending, text_hidden, z_style, text_mask,
                                                  None if states is None else states[i], kpm=kpm,
                                                  gb=None if gbs is None else gbs[i],
-                                                 kv=None if kvs is None else kvs[i])
+                                                 kv=None if kvs is None else kvs[i], seq_lens=seq_lens)
             new_states.append(st)
         return x, pending, new_states
 
@@ -307,7 +310,9 @@ class MambaTTSDecoder(nn.Module):
             z_style: (B, d_style) style embedding.
             mamba_states: list of per-layer states (length == n_layers). Each
                 entry may be None for the first step.
-            step_index: int, absolute position index of this token (0-based).
+            step_index: int, absolute position index of this token (0-based);
+                or a (B,) integer tensor of per-row positions (rows of a
+                ragged batch sit at different positions).
             text_mask: optional (B, T_text) boolean mask for text padding.
 
         Returns:
@@ -325,8 +330,11 @@ class MambaTTSDecoder(nn.Module):
                                      ref_hidden, ref_mask)
 
         tok = self.token_embed(last_token)
-        pos_id = torch.tensor([step_index], device=device)
-        pos = self.pos_embed(pos_id)[None, :, :].expand(B_local, 1, -1)
+        if isinstance(step_index, torch.Tensor):
+            pos = self.pos_embed(step_index.to(device).reshape(B_local))[:, None, :]
+        else:
+            pos_id = torch.tensor([step_index], device=device)
+            pos = self.pos_embed(pos_id)[None, :, :].expand(B_local, 1, -1)
         x = (tok + pos).to(cd)                                               # no quant_embed (:217-221)
 
         text_hidden = text_hidden.to(cd)
@@ -337,7 +345,7 @@ class MambaTTSDecoder(nn.Module):
             return self._tail(x, pending), new_states
 
     @torch.no_grad()
-    def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, start_token=0,
+    def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, prompt_lengths=None, start_token=0,
                  text_mask=None, ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0,
                  logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32):
         """Generate up to `max_new_tokens` codec tokens on the device
@@ -350,6 +358,10 @@ class MambaTTSDecoder(nn.Module):
         prefilled through the scan path (equivalent to decode_step on each
         prompt token in turn: no quant_embed).  Without it generation starts
         from `start_token` at position 0.
+        prompt_lengths (B,), tensor or list, 1 <= len_b <= Tp: the prompt is
+        ragged and right-padded -- row b continues from its first len_b
+        tokens (the padding slots' values are ignored) at position len_b.
+        New token i of every row is column i of the result.
         logit_bias: fp32 (V,) or (B, V) added to the logits (-inf forbids a
         token); eos_id: a row that emits it is padded with pad_id from then
         on, and generation stops once every row has (polled every
@@ -365,7 +377,7 @@ class MambaTTSDecoder(nn.Module):
         if self._engine is None or self._engine.use_graph != use_graph:
             self._engine = DecodeEngine(self, use_graph=use_graph)
         return self._engine.generate(text_hidden, z_style, max_new_tokens, prompt_tokens=prompt_tokens,
-                                     start_token=start_token, text_mask=text_mask, ref_hidden=ref_hidden,
+                                     prompt_lengths=prompt_lengths, start_token=start_token, text_mask=text_mask, ref_hidden=ref_hidden,
                                      ref_mask=ref_mask, temperature=temperature, top_k=top_k, top_p=top_p,
                                      logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
                                      check_every=check_every)

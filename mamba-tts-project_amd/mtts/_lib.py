@@ -31,7 +31,7 @@ class ScanFwdArgs(C.Structure):
                 ("B_bs", i64), ("B_ls", i64), ("C_bs", i64), ("C_ls", i64),
                 ("u", vp), ("delta", vp), ("A", vp), ("Bm", vp), ("Cm", vp), ("D", vp), ("z", vp),
                 ("delta_bias", vp), ("h0", vp), ("out", vp), ("last_state", vp), ("ckpt", vp),
-                ("workspace", vp)]
+                ("workspace", vp), ("seqlens", vp)]
 
 
 class ScanBwdArgs(C.Structure):
@@ -47,7 +47,8 @@ class ScanBwdArgs(C.Structure):
 class ConvFwdArgs(C.Structure):
     _fields_ = [("batch", i32), ("dim", i32), ("seqlen", i32), ("width", i32), ("dtype", i32), ("silu", i32),
                 ("x_bs", i64), ("x_ls", i64), ("out_bs", i64), ("out_ls", i64),
-                ("x", vp), ("w", vp), ("bias", vp), ("conv_state_in", vp), ("out", vp), ("conv_state_out", vp)]
+                ("x", vp), ("w", vp), ("bias", vp), ("conv_state_in", vp), ("out", vp), ("conv_state_out", vp),
+                ("seqlens", vp)]
 
 
 class ConvBwdArgs(C.Structure):
@@ -100,7 +101,7 @@ class SampleArgs(C.Structure):
                 ("bias", vp), ("bias_ld", i64), ("temperature", f32), ("top_p", f32), ("seed", vp), ("step", vp),
                 ("advance", i32), ("step0", i32), ("pos", vp), ("tokens", vp), ("tok_stride", i64),
                 ("history", vp), ("hist_ld", i64), ("hist_cols", i32), ("eos_id", i32), ("pad_id", i32),
-                ("reserved_", i32), ("finished", vp), ("length", vp), ("unfinished", vp)]
+                ("pos_rows", i32), ("finished", vp), ("length", vp), ("unfinished", vp)]
 
 
 class RowMap(C.Structure):
@@ -202,6 +203,7 @@ _SIGS = {
     "mtts_adam_workspace": ([i64], i64),
     "mtts_clip_adam": ([vp, i32, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp], i32),
     "mtts_embed_sum": ([vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i64, vp, vp], i32),
+    "mtts_embed_sum_at": ([vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i64, vp, i64, i32, vp], i32),
     "mtts_embed_table_grad_workspace": ([i64, i32, i32], i64),
     "mtts_embed_table_grad": ([vp, i64, vp, i32, i64, i32, i32, vp, vp, vp], i32),
     "mtts_cast_tiles": ([i32, i32], i64),
@@ -224,6 +226,12 @@ def lib():
             raise RuntimeError(f"libmtts.so not found at {LIB_PATH}; run __graft_entry__.build() "
                                "(make -C mamba-tts-project_amd/mtts/csrc)")
         L = C.CDLL(LIB_PATH)
+        # ABI 15 grew by additions only, so a library built before them reports
+        # the same version: the newest symbol tells the two apart
+        if not hasattr(L, "mtts_embed_sum_at"):
+            raise RuntimeError(f"{LIB_PATH} is stale: it was built before mtts_embed_sum_at (ragged prompts) was "
+                               "added; rebuild it with __graft_entry__.build() "
+                               "(make -C mamba-tts-project_amd/mtts/csrc)")
         for name, (argt, rest) in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = argt

@@ -101,7 +101,8 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const MttsConvFwdArgs a) 
   }
 }
 
-// conv_state_out[b, c, k] = last K inputs of [conv_state_in ‖ x]
+// conv_state_out[b, c, k] = last K inputs of [conv_state_in ‖ x[b, :len_b]]
+// (len_b = seqlen, or the row's own clamp(seqlens[b], 0, seqlen))
 template <typename T>
 __global__ void conv_state_kernel(const MttsConvFwdArgs a) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -109,7 +110,8 @@ __global__ void conv_state_kernel(const MttsConvFwdArgs a) {
   const int k = idx % kK;
   const int c = (idx / kK) % a.dim;
   const int b = idx / ((int64_t)kK * a.dim);
-  const int t = a.seqlen - kK + k;
+  const int len = a.seqlens ? max(0, min(a.seqlens[b], a.seqlen)) : a.seqlen;
+  const int t = len - kK + k;
   float v;
   if (t >= 0) v = ldf((const T*)a.x + (int64_t)b * a.x_bs + (int64_t)t * a.x_ls + c);
   else v = a.conv_state_in ? a.conv_state_in[((int64_t)b * a.dim + c) * kK + (kK + t)] : 0.f;
@@ -553,6 +555,7 @@ extern "C" int mtts_causal_conv1d_bwd(const MttsConvBwdArgs* a, void* stream) {
   int rc = check_conv(&a->f);
   if (rc) return rc;
   MTTS_CHECK(a->dout && a->dx && a->dw && a->workspace, "conv1d_bwd: null tensor");
+  MTTS_CHECK(!a->f.seqlens, "conv1d_bwd: seqlens is inference only");
   const MttsConvFwdArgs& f = a->f;
   if (f.seqlen == 0) return MTTS_OK;
   hipStream_t st = (hipStream_t)stream;

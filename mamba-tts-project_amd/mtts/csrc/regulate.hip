@@ -222,8 +222,10 @@ extern "C" int mtts_length_regulate_bwd(const void* dout, int dtype, int batch, 
 // Embedding sum (mamba_decoder.py:167-171 prologue, train.py:115-131
 // embed_codec_tokens):  out[b,l,:] = tok_w[tok[b,l]] + q_w[qid[l]] + pos_w[pid[l]]
 // fp32 tables (the master parameters), int64 token ids, int32 per-position
-// quantizer / position ids shared by the batch; one wave per output row,
-// float4 table reads, fp32 sum, out in f32 or bf16.
+// quantizer / position ids shared by the batch (position ids per row with
+// pid_bs != 0: mtts_embed_sum_at); one wave per output row, float4 table
+// reads, fp32 sum, out in f32 or bf16.  n_pos > 0 range-checks the position
+// like the token.
 namespace mtts {
 
 template <typename T>
@@ -231,14 +233,16 @@ __global__ __launch_bounds__(256) void embed_sum_kernel(const int64_t* __restric
                                                         const int* __restrict__ qid, const int* __restrict__ pid,
                                                         const float* __restrict__ tw, const float* __restrict__ qw,
                                                         const float* __restrict__ pw, int L, int d, int V, int rpb,
-                                                        T* __restrict__ out, int64_t o_bs, int* __restrict__ err) {
+                                                        T* __restrict__ out, int64_t o_bs, int* __restrict__ err,
+                                                        int64_t pid_bs, int n_pos) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int l0 = blockIdx.x * rpb;
   for (int l = l0 + w; l < min(L, l0 + rpb); l += 4) {
     const int64_t t = tok[b * tok_bs + l];
     T* __restrict__ o = out + b * o_bs + (int64_t)l * d;
-    if (t < 0 || t >= V) {
+    const int ps = pid[b * pid_bs + l];
+    if (t < 0 || t >= V || (n_pos > 0 && (ps < 0 || ps >= n_pos))) {
       // nn.Embedding would raise; the host checks the flag (mtts.embed.check_errors,
       // the decode engine once per step).  The row is written as zeros so no
       // uninitialised memory flows on.
@@ -251,7 +255,7 @@ __global__ __launch_bounds__(256) void embed_sum_kernel(const int64_t* __restric
     }
     const float4* __restrict__ a = reinterpret_cast<const float4*>(tw + t * d);
     const float4* __restrict__ q = reinterpret_cast<const float4*>(qw + (int64_t)qid[l] * d);
-    const float4* __restrict__ p = reinterpret_cast<const float4*>(pw + (int64_t)pid[l] * d);
+    const float4* __restrict__ p = reinterpret_cast<const float4*>(pw + (int64_t)ps * d);
     for (int c = lane; c < d / 4; c += 64) {
       const float4 x = a[c], y = q[c], z = p[c];
       const float s0 = (x.x + z.x) + y.x, s1 = (x.y + z.y) + y.y, s2 = (x.z + z.z) + y.z, s3 = (x.w + z.w) + y.w;
@@ -267,9 +271,10 @@ __global__ __launch_bounds__(256) void embed_sum_kernel(const int64_t* __restric
 
 }  // namespace mtts
 
-extern "C" int mtts_embed_sum(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
-                              const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d,
-                              int vocab, void* out, int dtype, int64_t out_bs, int* err_flag, void* stream) {
+static int embed_sum_impl(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
+                          const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d,
+                          int vocab, void* out, int dtype, int64_t out_bs, int* err_flag, int64_t pos_bs, int n_pos,
+                          void* stream) {
   MTTS_CHECK(batch >= 0 && L >= 0 && d > 0 && vocab > 0, "embed_sum: bad args");
   MTTS_CHECK(d % 4 == 0, "embed_sum: d_model %% 4 != 0");
   MTTS_CHECK(dtype == MTTS_F32 || dtype == MTTS_BF16, "embed_sum: bad dtype");
@@ -282,12 +287,28 @@ extern "C" int mtts_embed_sum(const int64_t* tokens, int64_t tok_bs, const int* 
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MTTS_F32)
     hipLaunchKernelGGL(embed_sum_kernel<float>, grid, dim3(256), 0, st, tokens, tok_bs, quant_ids, pos_ids, tok_w, q_w,
-                       pos_w, L, d, vocab, rpb, (float*)out, out_bs, err_flag);
+                       pos_w, L, d, vocab, rpb, (float*)out, out_bs, err_flag, pos_bs, n_pos);
   else
     hipLaunchKernelGGL(embed_sum_kernel<bf16_t>, grid, dim3(256), 0, st, tokens, tok_bs, quant_ids, pos_ids, tok_w,
-                       q_w, pos_w, L, d, vocab, rpb, (bf16_t*)out, out_bs, err_flag);
+                       q_w, pos_w, L, d, vocab, rpb, (bf16_t*)out, out_bs, err_flag, pos_bs, n_pos);
   MTTS_LAUNCH_CHECK("embed_sum");
   return MTTS_OK;
+}
+
+extern "C" int mtts_embed_sum(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
+                              const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d,
+                              int vocab, void* out, int dtype, int64_t out_bs, int* err_flag, void* stream) {
+  return embed_sum_impl(tokens, tok_bs, quant_ids, pos_ids, tok_w, q_w, pos_w, batch, L, d, vocab, out, dtype, out_bs,
+                        err_flag, 0, 0, stream);
+}
+
+extern "C" int mtts_embed_sum_at(const int64_t* tokens, int64_t tok_bs, const int* quant_ids, const int* pos_ids,
+                                 const float* tok_w, const float* q_w, const float* pos_w, int batch, int L, int d,
+                                 int vocab, void* out, int dtype, int64_t out_bs, int* err_flag, int64_t pos_bs,
+                                 int n_pos, void* stream) {
+  MTTS_CHECK(n_pos > 0 && pos_bs >= 0, "embed_sum_at: bad n_pos / pos_bs");
+  return embed_sum_impl(tokens, tok_bs, quant_ids, pos_ids, tok_w, q_w, pos_w, batch, L, d, vocab, out, dtype, out_bs,
+                        err_flag, pos_bs, n_pos, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -231,9 +231,11 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
   }
 }
 
-// Behind the sampler: count the unfinished rows and advance the counters.
+// Behind the sampler: count the unfinished rows and advance the counters
+// (pos_rows > 0: `pos` holds that many per-row positions, all moved in lockstep).
 __global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* step, int* pos, const int* finished,
-                                                                        int rows, int* unfinished, int advance) {
+                                                                        int rows, int* unfinished, int advance,
+                                                                        int pos_rows) {
   __shared__ uint64_t slots[2][4];
   int phase = 0;
   uint32_t done = 0;
@@ -245,9 +247,11 @@ __global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* ste
     if (unfinished) *unfinished = rows - (int)done;
     if (advance) {
       if (step) *step += 1;
-      if (pos) *pos += 1;
+      if (pos && pos_rows <= 0) *pos += 1;
     }
   }
+  if (advance && pos && pos_rows > 0)
+    for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads) pos[r] += 1;
 }
 
 }  // namespace
@@ -270,6 +274,7 @@ extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
   MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols), "sample_tokens: bad history shape");
   MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens: unfinished needs finished");
   MTTS_CHECK(!a->advance || a->step, "sample_tokens: advance needs step");
+  MTTS_CHECK(a->pos_rows >= 0, "sample_tokens: pos_rows=%d must be >= 0", a->pos_rows);
   hipStream_t st = (hipStream_t)stream;
   SampleParams prm;
   prm.a = *a;
@@ -284,7 +289,7 @@ extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
   MTTS_LAUNCH_CHECK("sample_tokens");
   if (a->advance || a->unfinished) {
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
-                       a->rows, a->unfinished, a->advance);
+                       a->rows, a->unfinished, a->advance, a->pos_rows);
     MTTS_LAUNCH_CHECK("sample_tokens (advance)");
   }
   return MTTS_OK;

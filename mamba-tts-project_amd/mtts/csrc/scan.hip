@@ -224,7 +224,13 @@ constexpr int kRing = 3;    // forward: register sets in the prefetch ring
 using TrueT = std::integral_constant<bool, true>;
 using FalseT = std::integral_constant<bool, false>;
 
-template <int P, typename Tio, typename Tbc, int MODE, bool SP>
+// RAG (ragged batch, a.seqlens): row b scans only its first
+// Le = clamp(seqlens[b], 0, L) steps.  The segment grid still comes from L;
+// a segment's end is cut at Le, so the row's last tile takes the TAIL path
+// (loads clamped to step Le-1, delta = 0 past it) and a segment that starts
+// at or past Le runs no tile at all: it loads nothing and leaves h and S at
+// the identity.  Nothing at t >= Le is read or written.
+template <int P, typename Tio, typename Tbc, int MODE, bool SP, bool RAG = false>
 __global__ __launch_bounds__(kBlock, 4) void scan_fwd_kernel(const MttsScanFwdArgs a, const int seg_len,
                                                              float* __restrict__ seg) {
   constexpr int NS = kN / P;
@@ -241,7 +247,9 @@ __global__ __launch_bounds__(kBlock, 4) void scan_fwd_kernel(const MttsScanFwdAr
   const int L = a.seqlen;
   const int K = (L + seg_len - 1) / seg_len;
   const int t_begin = k * seg_len;
-  const int t_end = min(L, t_begin + seg_len);
+  int Le = L;  // this row's valid length
+  if constexpr (RAG) Le = max(0, min(a.seqlens[b], L));
+  const int t_end = RAG ? max(t_begin, min(Le, t_begin + seg_len)) : min(L, t_begin + seg_len);
 
   // Addressing: uniform (SGPR) base per timestep + one 32-bit per-lane offset,
   // so loads/stores use the saddr form with no per-access VALU index math.
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(kBlock, 4) void scan_fwd_kernel(const MttsScanFwdAr
   auto load_tile = [&](auto tail, int t0, TileRegs& X) __attribute__((always_inline)) {
     constexpr bool TAIL = decltype(tail)::value;
     if constexpr (TAIL) {
-      X.st.load(st0 + (int64_t)min(t0 + st_s, L - 1) * st_ls + (st_col % kN));
+      X.st.load(st0 + (int64_t)min(t0 + st_s, Le - 1) * st_ls + (st_col % kN));
     } else {
       X.st.load(st0 + (int64_t)t0 * st_ls + lst);
     }
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(kBlock, 4) void scan_fwd_kernel(const MttsScanFwdAr
     for (int g = 0; g < G; ++g) {
       const int tg = t0 + g * P;
       if constexpr (TAIL) {
-        const int ts = min(tg + j, L - 1);
+        const int ts = min(tg + j, Le - 1);
         X.u[g] = ldr(u0 + (int64_t)ts * a.u_ls + c);
         X.d[g] = ldr(d0 + (int64_t)ts * a.delta_ls + c);
         if constexpr (MODE == kFull) X.z[g] = ldr(z0 + (int64_t)ts * z_ls + c);
@@ -1732,6 +1740,7 @@ static int check_fwd(const MttsScanFwdArgs* a) {
                  (a->C_ls * esz) % 16 == 0 && (a->B_bs * esz) % 16 == 0 && (a->C_bs * esz) % 16 == 0,
              "scan: B/C rows must be 16-byte aligned");
   if (a->ckpt) MTTS_CHECK(a->ckpt_chunk == kSub, "scan: ckpt_chunk must be %d", kSub);
+  MTTS_CHECK(!(a->ckpt && a->seqlens), "scan: seqlens is inference only (no ckpt)");
   return MTTS_OK;
 }
 
@@ -2097,9 +2106,19 @@ template <int P, typename Tio, typename Tbc, bool SP>
 static void launch_fwd_sp(const MttsScanFwdArgs* a, const FwdPlan& pl, hipStream_t st) {
   const int nbx = (a->dim + kBlock / P - 1) / (kBlock / P);
   float* seg = (float*)a->workspace;
-  if (c1_ok(a)) {
+  if (!a->seqlens && c1_ok(a)) {
     if (a->z) launch_c1<Tio, Tbc, SP, true>(a, st);
     else launch_c1<Tio, Tbc, SP, false>(a, st);
+    return;
+  }
+  // ragged batch: always the generic kernel (the only one that cuts rows
+  // short), whatever MTTS_OVR_SCAN_PATH asks for; P and the segments still apply
+  if (a->seqlens) {
+    if (pl.K > 1)
+      hipLaunchKernelGGL((scan_fwd_kernel<P, Tio, Tbc, kState, SP, true>), dim3(nbx, a->batch, pl.K - 1),
+                         dim3(kBlock), 0, st, *a, pl.seg_len, seg);
+    hipLaunchKernelGGL((scan_fwd_kernel<P, Tio, Tbc, kFull, SP, true>), dim3(nbx, a->batch, pl.K), dim3(kBlock), 0,
+                       st, *a, pl.seg_len, seg);
     return;
   }
   // the LDS-DMA kernel addresses rows through buffer descriptors: a batch

@@ -24,7 +24,9 @@ Engine path (inference only: torch.no_grad, HIP tensors):
   * generate(): the loop around the step on the device -- one hipGraph of
     step + token sampler (csrc/sample.hip) replayed per token, the token,
     step and position counters never leaving HBM; a prompt prefilled through
-    the scan path.
+    the scan path.  Positions are per row ((B,) device buffers), so a ragged,
+    right-padded prompt batch (prompt_lengths) runs the same captured graph:
+    the prefill stops every row's scan / conv state at its own length.
 Numerics are those of the eager module path (tests/test_gpu_modules.py).
 Call `reset()` after modifying weights in place between decode steps.
 """
@@ -174,17 +176,17 @@ class DecodeEngine:
     def _embed(self, tok):
         """token_embed(last_token) + pos_embed(step_index) in the compute dtype
         (mamba_decoder.py:188-256; no quant_embed in decode_step) as ONE
-        mtts_embed_sum launch (a zero quantizer row, the step's position id
-        from the int32 buffer pos32) instead of two gathers, an add and a
+        mtts_embed_sum_at launch (a zero quantizer row, each row's position id
+        from the (B,) int32 buffer pos32) instead of two gathers, an add and a
         cast."""
         m, c = self.m, self.ctx
         B = c["B"]
         d = m.token_embed.weight.shape[1]
         out = torch.empty(B, d, device=tok.device, dtype=c["cd"])
         tw, pw = c["tok_w"], c["pos_w"]
-        L.call_raw("mtts_embed_sum", tok.data_ptr(), tok.stride(0), c["q0_id"].data_ptr(), self.pos32.data_ptr(),
+        L.call_raw("mtts_embed_sum_at", tok.data_ptr(), tok.stride(0), c["q0_id"].data_ptr(), self.pos32.data_ptr(),
                    tw.data_ptr(), c["q0_w"].data_ptr(), pw.data_ptr(), B, 1, d, tw.shape[0], out.data_ptr(),
-                   L.dtype_code(out), out.stride(0), _err_flag(tok.device).data_ptr())
+                   L.dtype_code(out), out.stride(0), _err_flag(tok.device).data_ptr(), 1, pw.shape[0])
         return out
 
     _PACKED = ("Win", "Wx", "Wout", "Wq", "Wo", "W1", "W2")
@@ -324,7 +326,7 @@ class DecodeEngine:
     def _step(self, tok, pos, states):
         m, c = self.m, self.ctx
         cd = c["cd"]
-        x = (F.embedding(tok, m.token_embed.weight) + F.embedding(pos, m.pos_embed.weight)[None]).to(cd)
+        x = (F.embedding(tok, m.token_embed.weight) + F.embedding(pos, m.pos_embed.weight)[:, None]).to(cd)
         x = x.view(c["B"], -1)                                               # (B, d)
         mm_ = _proj_rows if (self.use_rows and cd == torch.bfloat16) else _proj_blas
         pending = None
@@ -418,8 +420,9 @@ class DecodeEngine:
                 self.states.append((torch.zeros(B, mm.d_inner, mm.d_conv, device=dev),
                                     torch.zeros(B, mm.d_inner, mm.d_state, device=dev)))
             self.tok_buf = torch.zeros(B, 1, dtype=torch.long, device=dev)
-            self.pos_buf = torch.zeros(1, dtype=torch.long, device=dev)
-            self.pos32 = torch.zeros(1, dtype=torch.int32, device=dev)
+            # per-row positions: int64 for the eager step's F.embedding, int32 for the fused step
+            self.pos_buf = torch.zeros(B, dtype=torch.long, device=dev)
+            self.pos32 = torch.zeros(B, dtype=torch.int32, device=dev)
 
     # -- public ----------------------------------------------------------------
     @torch.no_grad()
@@ -440,12 +443,17 @@ class DecodeEngine:
                 st[0].copy_(given[0])
                 st[1].copy_(given[1])
         self.tok_buf.copy_(last_token)
-        if not 0 <= int(step_index) < m.pos_embed.num_embeddings:   # pos_embed(step_index) raises (:226)
-            raise IndexError("index out of range in self")
-        if self.fused:   # the fused step embeds through mtts_embed_sum (int32 position id)
-            self.pos32.fill_(int(step_index))
+        pbuf = self.pos32 if self.fused else self.pos_buf   # the fused step embeds int32 position ids
+        if isinstance(step_index, torch.Tensor) and step_index.dim() > 0:   # per-row positions
+            if tuple(step_index.shape) != (B,) or step_index.dtype.is_floating_point or step_index.dtype == torch.bool:
+                raise ValueError(f"decode_step: a tensor step_index must be ({B},) integers, one position per row")
+            if not (0 <= int(step_index.min()) and int(step_index.max()) < m.pos_embed.num_embeddings):
+                raise IndexError("index out of range in self")
+            pbuf.copy_(step_index)
         else:
-            self.pos_buf.fill_(int(step_index))
+            if not 0 <= int(step_index) < m.pos_embed.num_embeddings:   # pos_embed(step_index) raises (:226)
+                raise IndexError("index out of range in self")
+            pbuf.fill_(int(step_index))
         step = self._step_rows if self.fused else self._step
         if not self.use_graph:
             logits = step(self.tok_buf, self.pos_buf, self.states)
@@ -492,12 +500,15 @@ class DecodeEngine:
                 host=torch.zeros(cap, dtype=torch.int32, pin_memory=True))
         return self.gen
 
-    def _prefill(self, prompt, conds):
+    def _prefill(self, prompt, conds, lens=None):
         """The whole prompt through the parallel (scan) path: one embed_sum
         with a zero quantizer row (decode_step adds no quant_embed,
         mamba_decoder.py:217-221), the layer stack from empty states, the head
         on the last position.  The per-layer (conv_state, ssm_state) it returns
-        become the engine's states; returns the last position's logits (B, V)."""
+        become the engine's states; returns the last position's logits (B, V).
+        `lens` (B,) int32 on the device: the prompt is ragged and right-padded;
+        every layer's scan and conv state stop at the row's own length and the
+        head reads the row's position lens[b] - 1."""
         m, c = self.m, self.ctx
         text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
         cd = c["cd"]
@@ -507,8 +518,14 @@ class DecodeEngine:
         qid = torch.zeros(Tp, dtype=torch.long, device=prompt.device)
         x = embed_sum(prompt, qid, m.token_embed.weight, c["q0_w"], m.pos_embed.weight, cd)
         with cast_scope(m._gemm_weights(), cd):
-            x, pending, new_states = m._run_layers(x, th, z_style, tm, None)
-            logits = m._tail(x[:, -1:].contiguous(), None if pending is None else pending[:, -1:].contiguous())
+            if lens is None:
+                x, pending, new_states = m._run_layers(x, th, z_style, tm, None)
+                last = lambda t: t[:, -1:].contiguous()  # noqa: E731
+            else:
+                x, pending, new_states = m._run_layers(x, th, z_style, tm, None, seq_lens=lens)
+                rows, at = torch.arange(B, device=prompt.device), lens.long() - 1
+                last = lambda t: t[rows, at][:, None].contiguous()  # noqa: E731
+            logits = m._tail(last(x), None if pending is None else last(pending))
         for (cs, ss), (ncs, nss) in zip(self.states, new_states):
             cs.copy_(ncs)
             ss.copy_(nss)
@@ -517,7 +534,7 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, text_hidden, z_style, max_new_tokens, prompt_tokens=None, start_token=0, text_mask=None,
                  ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, eos_id=None,
-                 pad_id=0, seed=0, check_every=32):
+                 pad_id=0, seed=0, check_every=32, prompt_lengths=None):
         """Autoregressive generation on the device: each new token is one
         replay of a hipGraph holding the decode step and the sampler
         (csrc/sample.hip), which writes the token buffer the next step embeds,
@@ -527,6 +544,11 @@ class DecodeEngine:
         prefilled through the scan path (_prefill) and its last logits feed
         the first draw; prompt tokens sit at positions 0..Tp-1, new token i is
         drawn from the logits at position Tp-1+i and fed at Tp+i.
+        With prompt_lengths (B,), 1 <= len_b <= Tp, the prompt is ragged and
+        right-padded: one prefill over (B, max len) with per-row lengths, row
+        b's positions start at len_b - 1 and move in lockstep from there, and
+        new token i of every row is history column i.  Positions are device
+        data, so ragged and rectangular calls replay the same graph.
 
         The seed lives in device memory (a new seed replays the same graph);
         temperature / top_k / top_p / eos_id / pad_id key the graph cache.
@@ -549,6 +571,24 @@ class DecodeEngine:
                                           or prompt_tokens.shape[1] < 1):
             raise ValueError("generate: prompt_tokens must be (B, Tp) with Tp >= 1")
         Tp = 1 if prompt_tokens is None else prompt_tokens.shape[1]
+        lens = None
+        if prompt_lengths is not None:
+            if prompt_tokens is None:
+                raise ValueError("generate: prompt_lengths needs prompt_tokens")
+            pl = torch.as_tensor(prompt_lengths)
+            if tuple(pl.shape) != (B,) or pl.dtype.is_floating_point or pl.dtype == torch.bool:
+                raise ValueError(f"generate: prompt_lengths must be ({B},) integers")
+            lo, hi = int(pl.min()), int(pl.max())
+            if lo < 1 or hi > Tp:
+                raise ValueError(f"generate: prompt_lengths must lie in [1, Tp = {Tp}] (got {lo}..{hi})")
+            # columns past the longest row are padding in every row; equal lengths are a rectangular prompt
+            prompt_tokens, Tp = prompt_tokens[:, :hi], hi
+            if lo < hi:
+                lens = pl.to(device=dev, dtype=torch.int32)
+                # the padding slots' values are ignored: a valid id on a copy, before any check or embedding
+                keep = torch.arange(Tp, device=dev)[None, :] < lens[:, None]
+                prompt_tokens = torch.where(keep, prompt_tokens.to(dev), torch.zeros((), dtype=prompt_tokens.dtype,
+                                                                                      device=dev))
         if Tp + n_new - 1 > m.pos_embed.num_embeddings:
             raise IndexError(f"generate: {Tp} prompt + {n_new} new tokens need positions beyond pos_embed "
                              f"({m.pos_embed.num_embeddings}) (index out of range in self)")
@@ -621,10 +661,14 @@ class DecodeEngine:
             g["bias"].copy_(logit_bias.to(torch.float32).expand(B, V))
         issued = 0
         if Tp > 1:
-            logits0 = self._prefill(prompt_tokens.long(), conds)
+            logits0 = self._prefill(prompt_tokens.long(), conds, lens)
             self.prefill_logits = logits0
-            self.pos32.fill_(Tp - 1)
-            self.pos_buf.fill_(Tp - 1)
+            if lens is None:
+                self.pos32.fill_(Tp - 1)
+                self.pos_buf.fill_(Tp - 1)
+            else:                                   # row b continues from its own last prompt position
+                self.pos32.copy_(lens - 1)
+                self.pos_buf.copy_(lens - 1)
             draw(logits0)                           # token 0 from the prompt's last logits; pos -> Tp
             issued = 1
         elif prompt_tokens is not None:

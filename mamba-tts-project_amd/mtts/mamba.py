@@ -39,14 +39,20 @@ class MambaInnerFn(torch.autograd.Function):
     """(xz, params[, state]) -> (y, conv_state, ssm_state); y is pre-out_proj."""
 
     @staticmethod
-    def forward(ctx, xz, conv_w, conv_b, W_x, W_dt, A_log, D, dt_bias, conv_state_in, h0):
+    def forward(ctx, xz, conv_w, conv_b, W_x, W_dt, A_log, D, dt_bias, conv_state_in, h0, seq_lens=None):
+        # (needs_input_grad reports the inputs' requires_grad whatever the grad mode, and this
+        # forward always runs with grad mode off: the caller, Mamba._forward, refuses seq_lens
+        # when a graph would be recorded; here a ragged call just saves nothing)
+        ctx.ragged = seq_lens is not None
+        need = any(ctx.needs_input_grad) and not ctx.ragged
         cd = xz.dtype
         di = xz.shape[-1] // 2
         N = A_log.shape[1]
         r = W_dt.shape[1]
         Wx, Wdt = cast_weight(W_x, cd), cast_weight(W_dt, cd)
         x, z = xz[..., :di], xz[..., di:]
-        u, conv_state = ops.conv_fwd(x, conv_w, conv_b, True, state_in=conv_state_in, want_state=True)
+        u, conv_state = ops.conv_fwd(x, conv_w, conv_b, True, state_in=conv_state_in, want_state=True,
+                                     seq_lens=seq_lens)
         u2 = u.view(-1, di)
         # x_proj stays on hipBLASLt (21 us vs 25 for SKINNY_N at C2, tools/skinny_ab.py);
         # dt_proj on the SMALL_K MFMA kernel (csrc/skinny.hip) when the shapes allow
@@ -58,9 +64,10 @@ class MambaInnerFn(torch.autograd.Function):
             *u.shape[:-1], di)
         # A = -exp(A_log) is formed inside the scan kernels (a_is_log): no per-layer exp / neg launches
         A_log32 = A_log.detach().float().contiguous()
-        need = any(ctx.needs_input_grad)
+        # ragged: the scan leaves y past each row's length unwritten -> zeros, not stale memory
+        y0 = None if seq_lens is None else torch.zeros_like(u)
         y, last, ckpt = ops.scan_fwd(u, delta, A_log32, Bm, Cm, D, z, dt_bias, True, h0, want_last=True,
-                                     want_ckpt=need, a_is_log=True)
+                                     want_ckpt=need, out=y0, a_is_log=True, seq_lens=seq_lens)
         if need:
             ctx.save_for_backward(xz, conv_w, conv_b, W_x, W_dt, A_log, D, dt_bias, u, x_dbl, delta, ckpt,
                                   conv_state_in, h0, A_log32)
@@ -70,6 +77,8 @@ class MambaInnerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _dconv, _dlast):
+        if ctx.ragged:
+            raise RuntimeError("Mamba: seq_lens (a ragged batch) is inference only: there is no backward")
         (xz, conv_w, conv_b, W_x, W_dt, A_log, D, dt_bias, u, x_dbl, delta, ckpt,
          conv_state_in, h0, A_log32) = ctx.saved_tensors
         if dy is None:   # grads are not materialised: y unused downstream
@@ -124,7 +133,7 @@ class MambaInnerFn(torch.autograd.Function):
         return (dxz, dw.reshape(conv_w.shape).to(conv_w.dtype), db.to(conv_b.dtype),
                 None if dW_x is None else dW_x.to(W_x.dtype), None if dW_dt is None else dW_dt.to(W_dt.dtype),
                 dA_log, dD.to(D.dtype), dbias.to(dt_bias.dtype), dstate,
-                None if dh0 is None else dh0.to(h0.dtype))
+                None if dh0 is None else dh0.to(h0.dtype), None)
 
 
 def _conv_state_grad(x, conv_w, conv_b, state, du):
@@ -191,24 +200,33 @@ class Mamba(nn.Module):
     def _w(self, lin, cd):
         return cast_weight(lin.weight, cd)
 
-    def forward(self, x, state=None):
-        """x (B, L, d) -> (out (B, L, d), (conv_state, ssm_state))."""
+    def forward(self, x, state=None, seq_lens=None):
+        """x (B, L, d) -> (out (B, L, d), (conv_state, ssm_state)).
+        seq_lens (B,) integers: x is a ragged, right-padded batch; the returned
+        states are each row's after its own seq_lens[b] steps, and out past a
+        row's length is meaningless.  Inference only (RuntimeError when a
+        gradient is required)."""
         if not x.is_cuda:
             raise RuntimeError("mtts.Mamba runs on the HIP kernels only (no CPU path)")
         with cast_scope():
-            return self._forward(x, state)
+            return self._forward(x, state, seq_lens)
 
-    def _forward(self, x, state):
+    def _forward(self, x, state, seq_lens=None):
         Bsz, Ln, _ = x.shape
-        if state is not None and Ln == 1:
+        if state is not None and Ln == 1 and seq_lens is None:
             return self.step(x, state)
+        if seq_lens is not None:
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+                raise RuntimeError("Mamba: seq_lens (a ragged batch) is inference only; run it under "
+                                   "torch.no_grad()")
+            seq_lens = ops._seq_lens(seq_lens, Bsz, x.device, "Mamba")
         xz = linear(x, self.in_proj.weight, self.in_proj.bias)
         conv_state_in = h0 = None
         if state is not None:
             conv_state_in, h0 = state
         y, conv_state, ssm_state = MambaInnerFn.apply(
             xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
-            self.A_log, self.D, self.dt_proj.bias, conv_state_in, h0)
+            self.A_log, self.D, self.dt_proj.bias, conv_state_in, h0, seq_lens)
         out = linear(y, self.out_proj.weight, self.out_proj.bias)
         return out, (conv_state, ssm_state)
 

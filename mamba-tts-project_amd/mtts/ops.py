@@ -46,6 +46,17 @@ def _bc(t):
 # ---------------------------------------------------------------------------
 # selective scan (channel-last)
 # ---------------------------------------------------------------------------
+def _seq_lens(seq_lens, batch, dev, what):
+    """Per-row valid lengths as the (B,) int32 device tensor the kernels read
+    (anything else is converted once)."""
+    if seq_lens is None:
+        return None
+    t = torch.as_tensor(seq_lens)
+    if t.dim() != 1 or t.shape[0] != batch or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{what}: seq_lens must be {batch} integers, one per batch row")
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
 def _scan_args(u, delta, A, Bm, Cm, D, z, delta_bias, softplus, h0, out, last, ckpt, a_is_log=False):
     Bsz, Ln, Dm = u.shape
     for t in (u, delta, out) + ((z,) if z is not None else ()):
@@ -71,12 +82,19 @@ def _scan_args(u, delta, A, Bm, Cm, D, z, delta_bias, softplus, h0, out, last, c
 
 
 def scan_fwd(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, softplus=True, h0=None,
-             want_last=False, want_ckpt=False, out=None, a_is_log=False):
+             want_last=False, want_ckpt=False, out=None, a_is_log=False, seq_lens=None):
     """u, delta, z: (B, L, D) channel-last; Bm, Cm: (B, L, N); A: (D, N) fp32
     (a_is_log: A holds A_log, the kernels use -exp(A_log)).
+    seq_lens (B,) int32 device tensor (or anything converted once to it): a
+    ragged, right-padded batch -- row b scans its first seq_lens[b] steps only,
+    last_state[b] is the state after them, out[b, seq_lens[b]:] is left
+    unwritten and no input there is read.  Inference only (no want_ckpt).
     Returns (out, last_state | None, ckpt | None)."""
     _check_cuda(u, delta, A, Bm, Cm, D, z, delta_bias, h0)
     Bsz, Ln, Dm = u.shape
+    if seq_lens is not None and want_ckpt:
+        raise ValueError("scan: seq_lens is inference only (want_ckpt must be False)")
+    seq_lens = _seq_lens(seq_lens, Bsz, u.device, "scan")
     N = A.shape[1]
     if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype):
         raise TypeError("scan: u/delta/z must share a dtype")
@@ -92,7 +110,7 @@ def scan_fwd(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, softplus=True
     a = _scan_args(u, delta, A, Bm, Cm, D, z, delta_bias, softplus, h0, out, last, ckpt, a_is_log)
     wsz = L.lib().mtts_selective_scan_fwd_workspace(Bsz, Dm, Ln, N)
     ws = torch.empty(wsz, device=u.device, dtype=torch.uint8) if wsz > 0 else None
-    a.workspace = L.ptr(ws)
+    a.workspace, a.seqlens = L.ptr(ws), L.ptr(seq_lens)
     L.call("mtts_selective_scan_fwd", a)
     return out, last, ckpt
 
@@ -187,8 +205,11 @@ def _conv_args(x, w, bias, silu, state_in, out, state_out):
     return a
 
 
-def conv_fwd(x, w, bias=None, silu=True, state_in=None, want_state=False, out=None):
-    """x (B, L, D) channel-last (may be a strided view); w (D, K)."""
+def conv_fwd(x, w, bias=None, silu=True, state_in=None, want_state=False, out=None, seq_lens=None):
+    """x (B, L, D) channel-last (may be a strided view); w (D, K).
+    seq_lens (B,) int32: the returned state of row b is the window ending at
+    its own length, the last K inputs of [state_in[b] ‖ x[b, :seq_lens[b]]];
+    the convolution output does not depend on it."""
     _check_cuda(x, w, bias, state_in)
     if x.stride(-1) != 1:
         x = x.contiguous()
@@ -197,7 +218,9 @@ def conv_fwd(x, w, bias=None, silu=True, state_in=None, want_state=False, out=No
     bias, state_in = _f32c(bias), _f32c(state_in)
     out = torch.empty(Bsz, Ln, Dm, device=x.device, dtype=x.dtype) if out is None else out
     st = torch.empty(Bsz, Dm, w.shape[1], device=x.device, dtype=torch.float32) if want_state else None
-    L.call("mtts_causal_conv1d_fwd", _conv_args(x, w, bias, silu, state_in, out, st))
+    a = _conv_args(x, w, bias, silu, state_in, out, st)
+    a.seqlens = L.ptr(_seq_lens(seq_lens, Bsz, x.device, "conv"))
+    L.call("mtts_causal_conv1d_fwd", a)
     return out, st
 
 
@@ -816,7 +839,8 @@ def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=Non
     seed (int64) / step (int32): ints, or one-element device tensors read at
     run time -- capture the call once and every replay draws from what the
     buffers hold; advance=True adds one to `step` (and to the int32 device
-    counter `pos`, when given) behind the draw.
+    counter `pos`, when given: one element, or (rows,) per-row positions that
+    all move in lockstep, finished rows included) behind the draw.
     out: int64 destination, any view with one element per row (default: a new
     (rows,) tensor).  history (rows, n) int64: column step - step0 also
     receives the token.  finished (rows,) int32 / length (rows,) int64 /
@@ -847,9 +871,9 @@ def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=Non
     step_t = _dev_scalar(step, torch.int32, dev, "step")
     a.seed, a.step, a.advance, a.step0 = seed_t.data_ptr(), step_t.data_ptr(), int(bool(advance)), int(step0)
     if pos is not None:
-        if pos.dtype != torch.int32 or pos.numel() != 1:
-            raise ValueError("sample_tokens: pos must be a one-element int32 tensor")
-        a.pos = pos.data_ptr()
+        if pos.dtype != torch.int32 or not pos.is_contiguous() or (pos.numel() != 1 and tuple(pos.shape) != (rows,)):
+            raise ValueError("sample_tokens: pos must be a one-element or a contiguous (rows,) int32 tensor")
+        a.pos, a.pos_rows = pos.data_ptr(), rows if pos.numel() > 1 else 0
     if out is None:
         out = torch.empty(rows, dtype=torch.int64, device=dev)
     if out.dtype != torch.int64 or out.numel() != rows:

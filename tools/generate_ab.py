@@ -4,7 +4,12 @@ on the device) and of decode_step + torch softmax / top-k / cumsum /
 multinomial with the token kept on the device, at C4 (12 layers, d_model
 1024, B = 32, bf16) over 512 steps, timed with HIP events, three interleaved
 repeats each; vocabulary 10 and 1024, greedy and top_k=50 / top_p=0.9.
-python tools/generate_ab.py [--steps 512] [--out FILE]"""
+--ragged runs the ragged-prompt leg instead (vocabulary 1024, greedy): a
+(32, 512) right-padded prompt with lengths uniform in [64, 512] -- the
+prefill with prompt_lengths against the rectangular prefill and against
+stepping the prompt columns through decode_step, and the per-token time of
+the ragged continuation against the rectangular one (the same graph).
+python tools/generate_ab.py [--steps 512] [--ragged] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -40,14 +45,73 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
+def ragged_leg(n, dev, lines):
+    import mamba_decoder
+    vocab, Tp = 1024, 512
+    c = dict(bench.C2)
+    c["B"] = 32
+    torch.manual_seed(0)
+    m = mamba_decoder.MambaTTSDecoder(vocab, d_model=c["d_model"], n_layers=c["n_layers"], n_heads=c["n_heads"],
+                                      d_ff=c["d_ff"], d_style=c["d_style"]).to(dev).eval()
+    m.compute_dtype = torch.bfloat16
+    _, text, z, mask = bench.make_batch(c, dev, 7)
+    g = torch.Generator().manual_seed(3)
+    lens = torch.randint(64, Tp + 1, (32,), generator=g)
+    lens[0] = Tp
+    prompt = torch.randint(0, vocab, (32, Tp), generator=g).to(dev)
+    kw = dict(temperature=0.0, text_mask=mask, seed=1)
+
+    def rect(k):
+        m.generate(text, z, k, prompt_tokens=prompt, **kw)
+
+    def rag(k):
+        m.generate(text, z, k, prompt_tokens=prompt, prompt_lengths=lens, **kw)
+
+    def steps():   # what a caller does without prompt_lengths: one decode_step per prompt column
+        with torch.no_grad():
+            states = [None] * c["n_layers"]
+            for t in range(Tp):
+                _, states = m.decode_step(prompt[:, t:t + 1], text, z, states, t, text_mask=mask)
+
+    for f in (rect, rag):
+        f(n + 1)
+    steps()
+    res = {k: [] for k in ("rect1", "rag1", "rectn", "ragn", "steps")}
+    for _ in range(3):
+        res["rect1"].append(timed(lambda: rect(1)))
+        res["rag1"].append(timed(lambda: rag(1)))
+        res["rectn"].append(timed(lambda: rect(n + 1)))
+        res["ragn"].append(timed(lambda: rag(n + 1)))
+        res["steps"].append(timed(steps))
+    fmt = lambda v: f"{min(v):8.2f} (" + " ".join(f"{x:.2f}" for x in v) + ")"  # noqa: E731
+    lines.append(f"ragged prompts, C4 (12L d=1024 B=32 bf16), vocab {vocab}, Tp {Tp}, lengths uniform in [64, {Tp}] "
+                 f"(mean {lens.float().mean():.0f}); ms, three repeats, min first")
+    lines.append(f"prefill + first token, rectangular (32 x {Tp})   {fmt(res['rect1'])}")
+    lines.append(f"prefill + first token, prompt_lengths            {fmt(res['rag1'])}")
+    lines.append(f"{Tp} decode_steps over the prompt columns          {fmt(res['steps'])}")
+    per = {k: [(a - b) * 1e3 / n for a, b in zip(res[k + "n"], res[k + "1"])] for k in ("rect", "rag")}
+    lines.append(f"us per token after the prefill ({n} tokens): rectangular " + fmt(per["rect"]).strip()
+                 + "  ragged " + fmt(per["rag"]).strip() + f"  graphs captured {len(m._engine.gen_graphs)}")
+    for ln in lines[-5:]:
+        print(ln, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=512)
+    ap.add_argument("--ragged", action="store_true", help="run the ragged-prompt leg instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
+    if args.ragged:
+        lines = []
+        ragged_leg(n, dev, lines)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     lines = [f"generate vs decode_step + torch sampling, C4 (12L d=1024 B=32 bf16), {n} steps, us per token "
              "(three repeats; spread = max - min of the loop's)"]
     for vocab in (10, 1024):
