@@ -676,10 +676,26 @@ int mtts_gemm(const MttsGemmArgs* a, void* stream);
  * A_i^T B_i (+ C_i when beta_i = 1) with fp32 out, no epilogue, no split-K,
  * in ONE launch; every output tile reduces its problem's whole K in one
  * workgroup (no partial slabs, no reduce pass).  Put the longest-K problems
- * first.  The deferred weight-gradient engine (mtts/wgrad.py) gathers a decoder
- * layer's projection weight gradients (mamba_decoder.py:29-43 in/out_proj,
- * MHA q/kv/out, FFN) into one such launch. */
+ * first.  The problems are a decoder layer's projection weight gradients
+ * (mamba_decoder.py:29-43 in/out_proj, MHA q/kv/out, FFN); the deferred
+ * weight-gradient engine (mtts/wgrad.py) now launches them through
+ * mtts_gemm_grouped_rounds below. */
 int mtts_gemm_grouped(const MttsGemmArgs* probs, int n, void* stream);
+
+/* The same problems in a launch that fills whole CU rounds (an addition to
+ * ABI 15: one new symbol, the version number stays): `n` (1..64) problems
+ * under the requirements above, and a tile grid that may be many times the CU
+ * count.  One workgroup runs per CU and every whole-K tile of equal K takes
+ * the same time, so the dispatcher runs the grid round after round; the ids
+ * are dealt to the XCDs round by round (consecutive ids on one XCD inside a
+ * round), so with the longest-K problems first the short tiles fall into the
+ * last round.  Every tile is computed exactly as by mtts_gemm_grouped (same
+ * body, same reduction order: bit-identical outputs).  The problem table
+ * travels in the kernel arguments (no device table, no allocation, no host
+ * synchronisation; captured by value in a hipGraph).  mtts/wgrad.py gathers
+ * SEVERAL decoder layers into one such launch: six C2 layers are 1248 long
+ * tiles, 5 rounds of 256 CUs instead of 6 rounds of 208. */
+int mtts_gemm_grouped_rounds(const MttsGemmArgs* probs, int n, void* stream);
 
 /* ------------------------------------------------------------------------
  * fp32 MFMA GEMM over WINDOWED row matrices (csrc/convgemm.hip, ABI 10): the

@@ -187,6 +187,7 @@ _SIGS = {
     "mtts_gemm_workspace": ([C.POINTER(GemmArgs)], i64),
     "mtts_gemm": ([C.POINTER(GemmArgs), vp], i32),
     "mtts_gemm_grouped": ([C.POINTER(GemmArgs), i32, vp], i32),
+    "mtts_gemm_grouped_rounds": ([C.POINTER(GemmArgs), i32, vp], i32),
     "mtts_convgemm": ([C.POINTER(ConvGemmArgs), vp], i32),
     "mtts_convgemm_workspace": ([C.POINTER(ConvGemmArgs)], i64),
     "mtts_gemm_skinny": ([C.POINTER(SkinnyArgs), vp], i32),
@@ -227,11 +228,13 @@ def lib():
                                "(make -C mamba-tts-project_amd/mtts/csrc)")
         L = C.CDLL(LIB_PATH)
         # ABI 15 grew by additions only, so a library built before them reports
-        # the same version: the newest symbol tells the two apart
-        if not hasattr(L, "mtts_embed_sum_at"):
-            raise RuntimeError(f"{LIB_PATH} is stale: it was built before mtts_embed_sum_at (ragged prompts) was "
-                               "added; rebuild it with __graft_entry__.build() "
-                               "(make -C mamba-tts-project_amd/mtts/csrc)")
+        # the same version: the added symbols tell them apart
+        for sym, what in (("mtts_embed_sum_at", "ragged prompts"),
+                          ("mtts_gemm_grouped_rounds", "round-filling weight gradients")):
+            if not hasattr(L, sym):
+                raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
+                                   "added; rebuild it with __graft_entry__.build() "
+                                   "(make -C mamba-tts-project_amd/mtts/csrc)")
         for name, (argt, rest) in _SIGS.items():
             fn = getattr(L, name)
             fn.argtypes = argt

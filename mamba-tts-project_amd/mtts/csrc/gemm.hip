@@ -40,6 +40,8 @@
 //    gelu'(pre-activation)); fp32 out with beta·C accumulate (wgrad).
 #include "common.h"
 
+#include <algorithm>
+#include <cstddef>
 #include <type_traits>
 
 namespace mtts {
@@ -993,6 +995,82 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_pp_grouped_kernel(const Grou
   gemm_pp_body<AK, BKM, EPI, OUT_F32>(q, wid - t0);
 }
 
+// Round-filling form: up to kRoundsMax problems and a tile grid of many times
+// the CU count in one launch (mtts/wgrad.py gathers several decoder layers).
+// One workgroup runs per CU and every long tile takes the same time, so the
+// dispatcher itself runs the grid round after round of `round` workgroups:
+// 6 C2 layers are 1248 long tiles = 4 full rounds + 224, against 6 rounds of
+// 208 one layer at a time.  No flags, counters or partial slabs: each tile is
+// gemm_pp_body over its problem's whole K, as in the kernel above.
+//  * A problem is packed to 56 bytes (TN, fp32 out, one split: three pointers,
+//    32-bit leading dimensions -- the host checks the spans fit 31 bits --
+//    m / n / k and beta; tiles and the L2 group are derived here), so 64 of
+//    them plus tile_end[] stay under 4 KiB of kernel arguments: the table is
+//    captured by value in a hipGraph, no device table, no allocation.
+//  * The entry is read with a wave-uniform index through the kernel-argument
+//    segment pointer (scalar loads); indexing the by-value struct itself
+//    would copy it to scratch, and 64 static selects of 14 dwords would cost
+//    ~900 scalar instructions per workgroup.
+//  * Work order: xcd_work_id() over the WHOLE grid would hand each XCD one
+//    contiguous eighth of the ids, i.e. all the short-K tiles at the end to
+//    the last XCD and 6 rounds of long tiles to the others.  Here the grid is
+//    cut into rounds of `round` ids (the CU count, a multiple of 8) and the
+//    XCD renumbering applies inside each round: every round spreads over all
+//    XCDs, an XCD still holds consecutive ids, and the short tiles at the end
+//    of the id range land in the last rounds.
+constexpr int kRoundsMax = 64;
+struct RoundProb {
+  const bf16_t* a;
+  const bf16_t* b;
+  void* c;
+  int lda, ldb, ldc;
+  int m, n, k;
+  float beta;
+  int pad_;
+};
+struct RoundParams {
+  RoundProb p[kRoundsMax];    // first member: the kernel reads it at kernel-argument offset 0
+  int tile_end[kRoundsMax];   // exclusive prefix sums of the problems' tile counts
+  int n;
+  int round;                  // workgroups resident at once (CU count rounded down to 8)
+};
+static_assert(sizeof(RoundProb) == 56 && offsetof(RoundParams, p) == 0 && sizeof(RoundParams) <= 4096,
+              "round-filling problem table must fit the kernel arguments");
+static_assert(offsetof(RoundProb, lda) == 24 && offsetof(RoundProb, ldc) == 32 && offsetof(RoundProb, n) == 40 &&
+              offsetof(RoundProb, beta) == 48, "gemm_pp_rounds_kernel reads RoundProb as qwords");
+
+__device__ __forceinline__ int round_work_id(int round) {
+  const int bid = blockIdx.x;
+  const int b = bid % round, r0 = bid - b;
+  const int nwg = min(round, (int)gridDim.x - r0);   // the last round may be short
+  const int q8 = nwg / 8, r8 = nwg % 8, xcd = b % 8;
+  return r0 + (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + b / 8;
+}
+
+__global__ __launch_bounds__(kThreads, 1) void gemm_pp_rounds_kernel(const RoundParams G) {
+  const int wid = round_work_id(G.round);
+  int i = 0, t0 = 0;
+#pragma unroll
+  for (int j = 0; j + 1 < kRoundsMax; ++j)
+    if (j + 1 < G.n && wid >= G.tile_end[j]) { i = j + 1; t0 = G.tile_end[j]; }
+  GemmParams q{};
+#if defined(__HIP_DEVICE_COMPILE__)
+  // entry i as 7 qwords (RoundProb's layout) from the constant address space
+  typedef const __attribute__((address_space(4))) uint64_t* KArg;
+  const KArg e = (KArg)__builtin_amdgcn_kernarg_segment_ptr() +
+                 __builtin_amdgcn_readfirstlane(i) * (int)(sizeof(RoundProb) / 8);
+  const uint64_t ld_ab = e[3], ldc_m = e[4], n_k = e[5];
+  q.a = (const bf16_t*)e[0]; q.b = (const bf16_t*)e[1]; q.c = (void*)e[2];
+  q.lda = (int)(uint32_t)ld_ab; q.ldb = (int)(ld_ab >> 32); q.ldc = (int)(uint32_t)ldc_m;
+  q.m = (int)(ldc_m >> 32); q.n = (int)(uint32_t)n_k; q.k = (int)(n_k >> 32);
+  q.beta = __uint_as_float((uint32_t)e[6]);
+#endif
+  q.tiles_m = (q.m + kTile - 1) / kTile; q.tiles_n = (q.n + kTile - 1) / kTile;
+  q.splits = 1;
+  q.group = min(q.tiles_m, 4);
+  gemm_pp_body<false, false, 0, true>(q, wid - t0);
+}
+
 // ---------------------------------------------------------------------------
 // Four-wave form (round 5, NT): the same 256x256 output tile on 4 waves
 // (2 M x 2 N, one per SIMD), 128x128 per wave (8x8 16x16 accumulator blocks,
@@ -1285,5 +1363,50 @@ extern "C" int mtts_gemm_grouped(const MttsGemmArgs* probs, int n, void* stream)
   hipLaunchKernelGGL((gemm_pp_grouped_kernel<false, false, 0, true>), dim3(tiles), dim3(kThreads), 0,
                      (hipStream_t)stream, G);
   MTTS_LAUNCH_CHECK("gemm_grouped");
+  return MTTS_OK;
+}
+
+extern "C" int mtts_gemm_grouped_rounds(const MttsGemmArgs* probs, int n, void* stream) {
+  using namespace mtts;
+  MTTS_CHECK(probs && n >= 1 && n <= kRoundsMax, "gemm_grouped_rounds: 1 <= n <= %d problems", kRoundsMax);
+  RoundParams G{};
+  int64_t tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    const MttsGemmArgs* a = probs + i;
+    MTTS_CHECK(a->a && a->b && a->c, "gemm_grouped_rounds[%d]: null pointer", i);
+    const int M = a->m, N = a->n, K = a->k;
+    MTTS_CHECK(a->layout == MTTS_GEMM_TN && a->out_dtype == 0 && a->epilogue == 0 && a->splits <= 1,
+               "gemm_grouped_rounds[%d]: TN, fp32 out, no epilogue, no split-K only", i);
+    MTTS_CHECK(M > 0 && N > 0 && K > 0 && K % kBK == 0, "gemm_grouped_rounds[%d]: m=%d n=%d k=%d (k %% 64 == 0)", i, M, N,
+               K);
+    MTTS_CHECK(N % 8 == 0 && M % 8 == 0, "gemm_grouped_rounds[%d]: m, n must be multiples of 8", i);
+    MTTS_CHECK(((uintptr_t)a->a | (uintptr_t)a->b) % 16 == 0 && a->lda % 8 == 0 && a->ldb % 8 == 0 &&
+               a->lda >= M && a->ldb >= N, "gemm_grouped_rounds[%d]: A / B alignment or leading dimension", i);
+    MTTS_CHECK(a->ldc % 4 == 0 && (uintptr_t)a->c % 16 == 0 && a->ldc >= N, "gemm_grouped_rounds[%d]: C alignment / ldc",
+               i);
+    MTTS_CHECK(a->beta == 0.f || a->beta == 1.f, "gemm_grouped_rounds[%d]: beta must be 0 or 1", i);
+    // also what lets lda / ldb / ldc travel as 32-bit fields
+    MTTS_CHECK((int64_t)(kBK - 1) * a->lda + M < (1ll << 31) && (int64_t)(kBK - 1) * a->ldb + N < (1ll << 31) &&
+               (int64_t)M * a->ldc * 4 < (1ll << 31),
+               "gemm_grouped_rounds[%d]: operand / C span exceeds the 32-bit offsets", i);
+    RoundProb& p = G.p[i];
+    p.a = (const bf16_t*)a->a; p.b = (const bf16_t*)a->b; p.c = a->c;
+    p.lda = (int)a->lda; p.ldb = (int)a->ldb; p.ldc = (int)a->ldc;
+    p.m = M; p.n = N; p.k = K;
+    p.beta = a->beta;
+    tiles += (int64_t)((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile);
+    MTTS_CHECK(tiles < (1ll << 31), "gemm_grouped_rounds[%d]: more than 2^31 output tiles", i);
+    G.tile_end[i] = (int)tiles;
+  }
+  G.n = n;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    cus = 0;
+  }
+  G.round = std::max(8, cus / 8 * 8);
+  hipLaunchKernelGGL(gemm_pp_rounds_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, (hipStream_t)stream, G);
+  MTTS_LAUNCH_CHECK("gemm_grouped_rounds");
   return MTTS_OK;
 }

@@ -8,18 +8,46 @@ C2), so run one by one they need split-K (fp32 partial slabs written, read
 back and summed by a second launch) to fill the chip.
 
 Here the layer's backward functions only QUEUE (dy, x, parameter, rows) and
-return no weight gradient; once the queue holds about one round of 256x256
-output tiles (one decoder layer: in_proj, out_proj, q, kv, out, FFN up and
-down -- 224 tiles at C2) the jobs run as ONE grouped launch
-(`mtts_gemm_grouped`): every tile reduces its problem's whole K in one
-workgroup, straight into the fp32 master gradient (no slabs, no reduce pass,
-no per-GEMM launch).  The rest of the queue is flushed by a callback at the
-end of the backward pass, before `loss.backward()` returns.
+return no weight gradient; the queued jobs run as ONE grouped launch
+(`mtts_gemm_grouped_rounds`): every 256x256 output tile reduces its problem's
+whole K in one workgroup, straight into the fp32 master gradient (no slabs, no
+reduce pass, no per-GEMM launch).  The rest of the queue is flushed by a
+callback at the end of the backward pass, before `loss.backward()` returns.
+
+When to flush.  The kernel holds 128 KiB of LDS, so one workgroup runs per CU
+and every tile of equal K takes the same time: a launch runs in ROUNDS of
+CU-count tiles.  One C2 decoder layer (in_proj, x_proj, dt_proj, out_proj, q,
+kv, out, FFN up and down) is 208 tiles over K = 16 k tokens plus 32 short text
+K/V tiles: flushed alone it is one round with 48 of 256 CUs idle (utilisation
+0.82), 12 rounds per step.  So the queue is cut into groups at the former
+flush points (GROUP_TILES tiles: one C2 layer), and at the end of its first
+group the queue plans how many groups to gather (`plan_groups`): the fewest
+that together fill whole rounds -- `utilisation()`, work / (CUs x makespan of
+a longest-first assignment), reaches FILL -- within the launch's problem limit
+and HOLD_BYTES of queued operands; when no number of groups does, it keeps
+flushing group by group as before.  FILL = 0.95 is a policy constant, not a
+measurement: at C2 one to five layers give 0.82 and six give 0.984 (1248 long
+tiles = 4 full rounds + 224, the 192 short tiles in the last round's free
+CUs), so any value between those makes six-layer launches: 10 rounds per step
+instead of 12.  Each tile is computed as before, so the gradients are
+bit-identical to per-layer flushing.  The queued layers' dy / x stay alive
+until the flush (0.7 GB per C2 layer; the step's peak, reached elsewhere, did
+not move: 13.75 GiB).  C5 (d_model 512, 80 tiles per layer) reaches its
+group boundary at 22 jobs, about 190 tiles: one or two such groups are about
+0.75 of one or two rounds and a third does not fit the problem table, so it
+plans 1 and runs as before.
+
+A GROUP_TILES below the default keeps its old meaning (flush as soon as that
+many tiles are queued; 1 = every submit flushes at once), and FILL_ROUNDS =
+False restores the per-layer flush.  Data-parallel runs keep the per-layer
+grouping too: with a listener registered (mtts.dp.GradAllReduce) holding six
+layers back would delay the bucketed all-reduces the listener exists to
+overlap with the backward, and that trade has not been measured on a
+multi-GPU node.
 
 The grouped launches can run on a side stream (SIDE_STREAM, off: no gain),
-so the next layer's data-gradient kernels fill the CUs the ~224 long tiles
-leave idle; the end-of-backward callback makes the caller's stream wait for
-it.
+so the next layer's data-gradient kernels fill the CUs the long tiles leave
+idle; the end-of-backward callback makes the caller's stream wait for it.
 
 Gradient semantics are autograd's: a parameter whose .grad is None gets a
 fresh gradient (or its data-parallel bucket view, mtts.dp), one whose .grad
@@ -44,14 +72,21 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import heapq
 
 import torch
 
 from . import _lib as L
 from . import gemm as G
 
-GROUP_TILES = 192       # flush once the queue holds this many 256x256 output tiles
-MAX_PROBLEMS = 24       # mtts_gemm_grouped's problem limit
+GROUP_TILES = 192       # tiles of one group (one C2 decoder layer); below the default: flush at that many tiles
+MAX_PROBLEMS = 64       # mtts_gemm_grouped_rounds' problem limit
+LAYER_PROBLEMS = 24     # per-layer grouping (GROUP_TILES below the default, listeners): flush near this many jobs
+FILL_ROUNDS = True      # hold groups until they fill whole CU rounds (module docstring)
+FILL = 0.95             # utilisation at which the queued groups count as whole rounds (policy, see above)
+HOLD_BYTES = 6 << 30    # flush when the queued dy / x reach this (six C2 layers: 4.2 GiB)
+_LAYER_TILES = GROUP_TILES
+_BK = 64                # the kernel's K-tile (tokens)
 # a flush with fewer tiles than this leaves most CUs idle for its whole-K
 # tiles (C5's d_model 512 layers: ~68 tiles of 640 K-tiles each): its jobs
 # run one by one on the split-K TN path instead (tools/c5_once.py trace:
@@ -80,11 +115,119 @@ class _Job:
         m, n = self.dy.shape[1], self.x.shape[1]
         return -(-m // G.TILE) * -(-n // G.TILE)
 
+    def nbytes(self):
+        return self.dy.numel() * self.dy.element_size() + self.x.numel() * self.x.element_size()
+
+
+def makespan(work, cus):
+    """K-tiles until the last of `cus` CUs is done with `work`, a list of
+    (tiles, K-tiles per tile), when the tiles go longest first to the CU that
+    is free first (one workgroup per CU: the dispatcher's order for a grid
+    sorted longest-K first).  Pure Python, no device."""
+    by_k = {}
+    for t, k in work:
+        if t > 0 and k > 0:
+            by_k[k] = by_k.get(k, 0) + t
+    loads = [0] * cus          # ascending
+    for k in sorted(by_k, reverse=True):
+        t = by_k[k]
+        if loads[-1] - loads[0] > k:     # uneven CUs: tile by tile until they are within one tile
+            heapq.heapify(loads)
+            top = max(loads)
+            while t and top - loads[0] > k:
+                new = loads[0] + k
+                heapq.heapreplace(loads, new)
+                top = max(top, new)
+                t -= 1
+            loads.sort()
+        # CUs within one tile of each other: every CU takes one tile before any takes a second
+        q, r = divmod(t, cus)
+        if q:
+            loads = [v + q * k for v in loads]
+        if r:
+            loads[:r] = [v + k for v in loads[:r]]
+            loads.sort()
+    return loads[-1]
+
+
+def utilisation(work, cus):
+    """Fraction of the CU x K-tile slots of a grouped launch of `work` (list of
+    (tiles, K-tiles per tile)) that compute: sum(tiles * K-tiles) / (cus *
+    makespan).  0.0 for an empty queue."""
+    total = sum(t * k for t, k in work if t > 0 and k > 0)
+    return total / (cus * makespan(work, cus)) if total else 0.0
+
+
+def plan_groups(work, nbytes, cus):
+    """How many groups like `work` (the first group of a queue: its (tiles,
+    K-tiles) list and the bytes its operands hold) to gather into one launch.
+    The backward repeats its layers, so n groups are taken to be n copies of
+    the first: the plan is the fewest groups whose utilisation reaches FILL
+    while their jobs fit the launch's problem table and their operands
+    HOLD_BYTES -- and 1, the former group-by-group flush, when no such number
+    exists (holding work back without filling rounds only costs memory)."""
+    n = 1
+    while n * len(work) <= MAX_PROBLEMS - 2 and n * nbytes <= HOLD_BYTES:
+        if utilisation(work * n, cus) >= FILL:
+            return n
+        n += 1
+    return 1
+
+
+class RoundQueue:
+    """Bookkeeping of the round-filling policy, free of tensors (the engine
+    below and the CPU tests drive it): add() every queued job, then ask
+    full() once per submit."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.work = []       # (tiles, K-tiles per tile) of the queued jobs
+        self.held = 0        # bytes of the queued dy / x
+        self.tiles = 0       # tiles and jobs queued since the last group boundary
+        self.jobs = 0
+        self.groups = 0      # groups complete
+        self.plan = 1        # groups to gather (plan_groups at the end of the first)
+
+    def add(self, tiles, ktiles, nbytes):
+        self.work.append((tiles, ktiles))
+        self.held += nbytes
+        self.tiles += tiles
+        self.jobs += 1
+
+    def full(self, cus):
+        """Flush now?  A group ends where the per-layer rule flushes
+        (GROUP_TILES tiles or nearly LAYER_PROBLEMS jobs); the first group
+        makes the plan, and the queue is flushed at the end of the plan's last
+        group, or earlier when the problem table or the byte cap is full."""
+        if len(self.work) >= MAX_PROBLEMS - 2:
+            return True
+        if self.tiles < GROUP_TILES and self.jobs < LAYER_PROBLEMS - 2:
+            return False
+        self.tiles = self.jobs = 0
+        self.groups += 1
+        if self.groups == 1:
+            self.plan = plan_groups(self.work, self.held, cus)
+        return self.groups >= self.plan or self.held >= HOLD_BYTES
+
+
+_cus = {}
+
+
+def cu_count(dev):
+    """CUs of the device the queued tensors live on (the policy's round size)."""
+    i = dev.index if dev.index is not None else torch.cuda.current_device()
+    if i not in _cus:
+        _cus[i] = torch.cuda.get_device_properties(i).multi_processor_count
+    return _cus[i]
+
 
 class _Engine:
     def __init__(self):
         self.jobs = []
         self.tiles = 0
+        self.queue = RoundQueue()
         self.callback_queued = False
         self.done = set()        # ids of params announced complete this backward
         self.covered = {}        # id(param) -> (param, [(r0, r1), ...] rows flushed this backward, overlapped)
@@ -215,7 +358,11 @@ def submit(jobs, narrow=False) -> bool:
         j = _Job(dy, x, p, rows)
         _E.jobs.append(j)
         _E.tiles += j.tiles()
-    if _E.tiles >= GROUP_TILES or len(_E.jobs) >= MAX_PROBLEMS - 2:
+        _E.queue.add(j.tiles(), dy.shape[0] // _BK, j.nbytes())
+    if not FILL_ROUNDS or _E.listeners or GROUP_TILES < _LAYER_TILES:   # per-layer grouping
+        if _E.tiles >= GROUP_TILES or len(_E.jobs) >= LAYER_PROBLEMS - 2:
+            flush()
+    elif _E.queue.full(cu_count(dy.device)):
         flush()
     return True
 
@@ -224,6 +371,7 @@ def flush():
     """Run every queued weight gradient (grouped launches) and publish the
     completed parameters' gradients."""
     jobs, _E.jobs, _E.tiles = _E.jobs, [], 0
+    _E.queue.clear()
     if not jobs:
         return
     if not (SIDE_STREAM and _E.callback_queued):
@@ -244,7 +392,9 @@ def _flush(jobs, side=None):
     # destinations: accumulate into an existing .grad; else the data-parallel
     # bucket view (mtts.dp) or a fresh tensor (zeroed when this flush does not
     # cover all of its rows)
-    dest = {}
+    dest, covered = {}, {}
+    for j in jobs:      # rows of each parameter this flush writes (one pass: a flush holds up to 62 jobs)
+        covered[id(j.param)] = covered.get(id(j.param), 0) + ((j.rows[1] - j.rows[0]) if j.rows else j.param.shape[0])
     for j in jobs:
         p = j.param
         if id(p) in dest:
@@ -252,7 +402,7 @@ def _flush(jobs, side=None):
         if p.grad is not None:
             dest[id(p)] = (p.grad, 1.0, False)
             continue
-        cover = sum((j2.rows[1] - j2.rows[0]) if j2.rows else p.shape[0] for j2 in jobs if j2.param is p)
+        cover = covered[id(p)]
         view = getattr(p, "_mtts_grad_view", None)
         full = cover >= p.shape[0]
         if view is not None:
@@ -316,6 +466,6 @@ def _launch(probs):
         a.a, a.b, a.c = dy.data_ptr(), x.data_ptr(), out.data_ptr()
         a.beta = beta
     lib = L.lib()
-    rc = lib.mtts_gemm_grouped(arr, len(probs), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = lib.mtts_gemm_grouped_rounds(arr, len(probs), C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != 0:
-        raise RuntimeError(f"mtts_gemm_grouped failed ({rc}): {lib.mtts_last_error().decode()}")
+        raise RuntimeError(f"mtts_gemm_grouped_rounds failed ({rc}): {lib.mtts_last_error().decode()}")
