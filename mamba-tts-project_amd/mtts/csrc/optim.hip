@@ -4,7 +4,8 @@
 // the number of tensors:
 //   1. per-chunk partial sums of g^2 (64 Ki elements per block, float4),
 //   2. one block: total = sqrt(sum of partials) in a fixed order,
-//      coef = min(1, max_norm / (total + 1e-6))   (clip_grad_norm_'s formula),
+//      coef = min(1, max_norm / (total + 1e-6))   (clip_grad_norm_'s formula;
+//      NaN when the norm is NaN, as torch's clamp gives),
 //      t = ++(*step_counter) and the bias corrections (device-side, so the
 //      whole training step can be captured in a hipGraph and replayed),
 //   3. per-chunk Adam on (p, g*coef, m, v) with torch's update:
@@ -85,7 +86,11 @@ __global__ __launch_bounds__(kAdamBlock) void norm_final_kernel(const float* __r
   if (threadIdx.x == 0) {
     const float total = sqrtf(s);
     out[0] = total;
-    out[1] = max_norm > 0.f ? fminf(1.f, max_norm / (total + 1e-6f)) : 1.f;
+    // torch's clamp(max_norm / (total + 1e-6), max=1): a NaN norm gives a NaN
+    // coefficient (fminf would return 1 and hide it), so one NaN gradient
+    // element turns every parameter NaN, as clip_grad_norm_ does
+    const float ratio = max_norm / (total + 1e-6f);
+    out[1] = max_norm > 0.f ? (ratio > 1.f ? 1.f : ratio) : 1.f;
     const int t = step_counter[0] + 1;
     step_counter[0] = t;
     const double bc1 = 1.0 - pow((double)h.b1, (double)t), bc2 = 1.0 - pow((double)h.b2, (double)t);

@@ -9,7 +9,14 @@ for the whole parameter list (mtts_clip_adam: partial sums of g^2, the norm
 and clip coefficient on device, then Adam on g * coef).  Gradients are left
 unclipped; `last_grad_norm` holds the total norm (device scalar).  The step
 count is kept on the device too, so a training step that ends in step()
-can be captured in a hipGraph (bench.py --graph).
+can be captured in a hipGraph (bench.py --graph).  A capture needs one eager
+step() before it (on the same parameters, and again after load_state_dict):
+the moments, the device step counter and the descriptor plan are created
+eagerly, never as nodes of the graph, where every replay would zero them
+again; step() raises otherwise.  What a captured graph reads and writes at
+every replay (descriptors, workspace, norm, step counter) lives as long as
+the optimizer.  A non-finite gradient norm gives a NaN clip coefficient, as
+clip_grad_norm_'s clamp does: every parameter of the group turns NaN.
 
 clip_into_optimizer is the torch-optimizer variant (norm by foreach, the
 clip folded into a fused torch Adam via grad_scale).
@@ -35,6 +42,11 @@ def same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a.shape == b.shape and all(n == 1 or sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()))
 
 
+NEEDS_EAGER_STEP = ("FusedClipAdam: take one eager step() before capturing (after construction and after "
+                    "load_state_dict): the moments, the device step counter and the descriptor plan must exist "
+                    "before the capture, or every replay would reset them")
+
+
 class FusedClipAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -44,8 +56,12 @@ class FusedClipAdam(torch.optim.Optimizer):
         self.max_grad_norm = max_grad_norm
         self.last_grad_norm = None
         self._plans = {}
+        # (plan, step counter) of every captured step: a replay uploads from the
+        # plan's pinned buffer and runs on its device buffers, so neither the
+        # plan cache's eviction nor load_state_dict may release them
+        self._captured = []
 
-    def _plan(self, ps, dev):
+    def _plan(self, ps, dev, dstep=None):
         """Device descriptor array of (p, g, exp_avg, exp_avg_sq).  Parameters
         and moments are fixed; gradients may move between steps (zero_grad
         set_to_none), so a changed list is re-uploaded from a pinned buffer
@@ -58,6 +74,8 @@ class FusedClipAdam(torch.optim.Optimizer):
         plan = self._plans.get(pkey)
         lib = L.lib()
         if plan is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(NEEDS_EAGER_STEP)
             ts = (L.AdamTensor * len(ps))()
             c0 = 0
             for i, p in enumerate(ps):
@@ -81,7 +99,7 @@ class FusedClipAdam(torch.optim.Optimizer):
             # addresses; the descriptors go into a pinned buffer reserved for
             # the capture (allocated before it; nothing rewrites it later), and
             # its upload is a captured copy
-            if plan.get("captured"):
+            if plan.get("captured") is not None:     # a tensor: its truth value would raise instead
                 raise RuntimeError("FusedClipAdam: one captured graph per parameter list")
             ts = plan["ts"]
             for i, p in enumerate(ps):
@@ -90,6 +108,7 @@ class FusedClipAdam(torch.optim.Optimizer):
             dev_buf = torch.empty(plan["cap_host"].numel(), dtype=torch.uint8, device=dev)
             dev_buf.copy_(plan["cap_host"], non_blocking=True)
             plan["captured"] = dev_buf
+            self._captured.append((plan, dstep))
             return dev_buf, plan["nch"], plan["ws"], plan["norm"]
         if plan["gkey"] != gkey:
             ts = plan["ts"]
@@ -122,6 +141,10 @@ class FusedClipAdam(torch.optim.Optimizer):
                 if p.grad.is_sparse or not dense(p) or not same_layout(p.grad, p):
                     raise ValueError("FusedClipAdam needs dense parameters and gradients of the same strides")
                 st = self.state[p]
+                if capturing and (not st or group.get("_dstep") is None):
+                    # created here they would be fills inside the graph: every
+                    # replay would zero the moments / reset the step counter
+                    raise RuntimeError(NEEDS_EAGER_STEP)
                 if not st:
                     st["step"] = torch.tensor(0.0)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
@@ -140,7 +163,7 @@ class FusedClipAdam(torch.optim.Optimizer):
             if not capturing:
                 for p in ps:
                     self.state[p]["step"] += 1
-            raw, nch, ws, norm = self._plan(ps, ps[0].device)
+            raw, nch, ws, norm = self._plan(ps, ps[0].device, dstep)
             b1, b2 = group["betas"]
             mx = float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0
             L.call_raw("mtts_clip_adam", raw.data_ptr(), len(ps), nch, dstep.data_ptr(), float(group["lr"]), float(b1),
@@ -168,7 +191,9 @@ class FusedClipAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """torch.optim.Adam.load_state_dict, then drop every cached descriptor
         plan (they point at the replaced moment tensors) and the device step
-        counters (re-seeded from the loaded state["step"] on the next step)."""
+        counters (re-seeded from the loaded state["step"] on the next step).
+        A graph captured before the load still steps the replaced moments:
+        take one eager step and capture again."""
         super().load_state_dict(state_dict)
         self._plans = {}
         for g in self.param_groups:

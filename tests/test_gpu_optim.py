@@ -5,13 +5,85 @@ CPU in float64 with the same parameters and gradients, over several steps.
 Tolerance: norm, exp_avg, exp_avg_sq 1e-5 relative; parameters 1e-4 of
 max|p| -- an fp32 update lr*m/(sqrt(v)+eps) differs from the float64 one by
 up to ~1e-2*lr where weight decay cancels a gradient down to ~eps (the
-fp32 rounding of g is then a large part of it)."""
+fp32 rounding of g is then a large part of it).
+
+The edge tests below the first one run at the benchmark's lr = 1e-4, where
+that parameter tolerance is a whole update wide, so they bound the update
+itself (test_optim_ref_cpu.update_close: max|dp - dp_ref| <= 1e-2 *
+max|dp_ref| per tensor, derived and proven to discriminate there) and keep
+1e-5 for the norm and the moments.  They cover: more chunks than
+norm_final_kernel's 256 threads, tensor sizes around the 65536-element chunk,
+pointers off 16-byte alignment (the scalar paths of sumsq_kernel and
+adam_kernel, which decide separately), gradients that move between steps,
+all-zero gradients, and a NaN / inf gradient element against torch's own
+float32 result.  The measured errors are kept in profiles/optim_parity.txt
+(rewritten when MTTS_OPTIM_PARITY names a file to write)."""
 import pytest
 import torch
 
 from test_gpu_ops import close, DEV
+from test_optim_ref_cpu import Twin, off_singular_point, record, rel_err, update_close, write_parity
 
 pytestmark = pytest.mark.gpu
+
+LR = 1e-4            # bench.py's
+BETAS = (0.9, 0.95)
+CHUNK = 65536        # csrc/optim.hip kAdamChunk
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _parity_report():
+    yield
+    write_parity()
+
+
+def check_after(name, opt, gp, before, twin, ref_before, total):
+    """After one step of both: norm, update and moments of `opt` against the float64 twin."""
+    errs = {"update": 0.0, "exp_avg": 0.0, "exp_avg_sq": 0.0}
+    if total is not None:
+        close(opt.last_grad_norm, total, rtol=1e-5, name=f"{name} norm")
+        errs["norm"] = rel_err(opt.last_grad_norm, total)
+    rm, rv = twin.moments()
+    for i, (p, b, rb, ra) in enumerate(zip(gp, before, ref_before, twin.values())):
+        errs["update"] = max(errs["update"], update_close(b, p, rb, ra, name=f"{name} param{i}"))
+        st = opt.state[p]
+        close(st["exp_avg"], rm[i], rtol=1e-5, name=f"{name} m{i}")
+        close(st["exp_avg_sq"], rv[i], rtol=1e-5, name=f"{name} v{i}")
+        errs["exp_avg"] = max(errs["exp_avg"], rel_err(st["exp_avg"], rm[i]))
+        errs["exp_avg_sq"] = max(errs["exp_avg_sq"], rel_err(st["exp_avg_sq"], rv[i]))
+    record(name.split("[")[0], **errs)
+
+
+def step_and_check(name, opt, gp, twin, grads):
+    """opt.step() on the gradients already set on gp (equal to the CPU `grads`), then the comparison."""
+    before = [p.detach().clone() for p in gp]
+    opt.step()
+    ref_before, total = twin.step(grads)
+    check_after(name, opt, gp, before, twin, ref_before, total)
+
+
+def make(shapes, wd=0.01, max_norm=1.0, seed=0):
+    from mtts.optim import FusedClipAdam
+    gen = torch.Generator().manual_seed(seed)
+    init = [torch.randn(*s, generator=gen) for s in shapes]
+    gp = [torch.nn.Parameter(t.clone().to(DEV)) for t in init]
+    opt = FusedClipAdam(gp, lr=LR, betas=BETAS, eps=1e-8, weight_decay=wd, max_grad_norm=max_norm)
+    return gen, init, gp, opt, Twin(init, LR, wd, max_norm)
+
+
+def rand_grads(gen, shapes, step):
+    return [torch.randn(*s, generator=gen) * (3.0 if step % 2 else 0.01) for s in shapes]
+
+
+def draw(gen, shapes, step, init, wd=0.01, max_norm=1.0):
+    """rand_grads, the first step's kept off the point where g * coef + wd * p
+    cancels to within eps (test_optim_ref_cpu: no fp32 Adam is accurate there)."""
+    grads = rand_grads(gen, shapes, step)
+    return off_singular_point(init, grads, wd, max_norm)[0] if step == 0 else grads
+
+
+def bits(t):
+    return t.detach().contiguous().view(torch.int32).cpu()
 
 SHAPES = [(4096, 1024), (7,), (65537,), (96, 2048), (3, 5, 2), (1,)]
 
@@ -35,12 +107,21 @@ def test_fused_clip_adam_vs_torch(max_norm, wd):
         total = None
         if max_norm is not None:
             total = torch.nn.utils.clip_grad_norm_(cp, max_norm)
+        before = [p.detach().clone() for p in gp]
+        ref_before = [p.detach().clone() for p in cp]
         opt.step()
         ref.step()
         if total is not None:
             close(opt.last_grad_norm, total, rtol=1e-5, name="norm")
         for i, (a, b) in enumerate(zip(gp, cp)):
             close(a, b.detach(), rtol=1e-4, name=f"param{i} step{step}")
+            # the update itself too, except the first step under weight decay: there u = g / (|g| + eps)
+            # with g = grad + wd*p has slope 1/eps where the two cancel to within eps, and float(0.01)
+            # is 2.2e-10 off 0.01, so such an element (about one in 3.6 M; this list holds 4.6 M) is
+            # off by up to 2 % of lr in any fp32 Adam (test_optim_ref_cpu's restatement: 3.5 % here)
+            if wd == 0.0 or step > 0:
+                record("fused_clip_adam_vs_torch (lr=1e-2)",
+                       update=update_close(before[i], a, ref_before[i], b.detach(), name=f"update{i} step{step}"))
             close(opt.state[a]["exp_avg"], ref.state[b]["exp_avg"], rtol=1e-5, name=f"m{i}")
             close(opt.state[a]["exp_avg_sq"], ref.state[b]["exp_avg_sq"], rtol=1e-5, name=f"v{i}")
     assert float(opt.state[gp[0]]["step"]) == 4.0
@@ -91,3 +172,192 @@ def test_fused_clip_adam_permuted_dense_parameter():
 def opt_state_strides_match(opt, p):
     st = opt.state[p]
     return st["exp_avg"].stride() == p.stride() and st["exp_avg_sq"].stride() == p.stride()
+
+
+# ------------------------------------------------------------- kernel edges
+@pytest.mark.parametrize("max_norm", [1.0, 1e6])
+def test_more_than_256_chunks(max_norm):
+    """303 chunks, so norm_final_kernel's 256-stride loop over the partials
+    takes a second, partial trip (chunks 256..302 are 47 of the small
+    tensors: 1.8e-3 of the squared norm, far above the 1e-5 bound), with the
+    clip binding (norm ~ 3.6 and ~ 1090 against 1) and not (against 1e6)."""
+    shapes = [(5,)] * 150 + [(2 * CHUNK + 3,)] + [(5,)] * 150
+    gen, init, gp, opt, twin = make(shapes, max_norm=max_norm)
+    for step in range(3):
+        grads = draw(gen, shapes, step, init, max_norm=max_norm)
+        for p, g in zip(gp, grads):
+            p.grad = g.to(DEV)
+        step_and_check(f"more_than_256_chunks[{max_norm}]", opt, gp, twin, grads)
+    (plan,) = opt._plans.values()
+    assert plan["nch"] == 303
+
+
+@pytest.mark.parametrize("numel", [CHUNK - 1, CHUNK, 2 * CHUNK, 2 * CHUNK + 3])
+def test_chunk_boundaries(numel):
+    """Sizes one under, at and past whole chunks, followed by a small tensor
+    whose chunk index depends on the first one's chunk count."""
+    shapes = [(numel,), (7,)]
+    gen, init, gp, opt, twin = make(shapes)
+    for step in range(2):
+        grads = draw(gen, shapes, step, init)
+        for p, g in zip(gp, grads):
+            p.grad = g.to(DEV)
+        step_and_check(f"chunk_boundaries[{numel}]", opt, gp, twin, grads)
+    (plan,) = opt._plans.values()
+    assert plan["nch"] == -(-numel // CHUNK) + 1
+
+
+P_SENTINEL = 12345.0
+
+
+def sliced(n, offset, fill):
+    """A buffer of n + offset + 9 elements filled with `fill`, and its [offset : offset + n] view."""
+    buf = torch.full((offset + n + 9,), fill, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    return buf, buf[offset:offset + n]
+
+
+def outside_equal(buf, snap, offset, n):
+    return torch.equal(bits(buf[:offset]), bits(snap[:offset])) and torch.equal(bits(buf[offset + n:]),
+                                                                                 bits(snap[offset + n:]))
+
+
+@pytest.mark.parametrize("n", [5, CHUNK + 5])
+@pytest.mark.parametrize("k,j", [(0, 1), (1, 0), (3, 3), (2, 0)])
+def test_unaligned_parameter_and_gradient(k, j, n):
+    """p = buf[k:k+n], p.grad = gbuf[j:j+n]: off 16-byte alignment the kernels
+    take their scalar paths, sumsq_kernel by the gradient alone and
+    adam_kernel by all four pointers, so (1, 0) and (2, 0) run a vector norm
+    beside a scalar update.  The parameter buffer holds a sentinel outside the
+    slice and the gradient buffer NaN (a read past the slice would poison the
+    norm); afterwards the sentinels and the whole gradient buffer are
+    bit-identical: the step leaves gradients unclipped."""
+    from mtts.optim import FusedClipAdam
+    gen = torch.Generator().manual_seed(0)
+    init = [torch.randn(n, generator=gen), torch.randn(7, generator=gen)]
+    buf, view = sliced(n, k, P_SENTINEL)
+    view.copy_(init[0])
+    gbuf, gview = sliced(n, j, float("nan"))
+    gp = [torch.nn.Parameter(view), torch.nn.Parameter(init[1].to(DEV))]
+    assert gp[0].data_ptr() == buf.data_ptr() + 4 * k and gview.data_ptr() == gbuf.data_ptr() + 4 * j
+    opt = FusedClipAdam(gp, lr=LR, betas=BETAS, eps=1e-8, weight_decay=0.01, max_grad_norm=1.0)
+    twin = Twin(init, LR, 0.01, 1.0)
+    snap = buf.clone()
+    for step in range(2):
+        grads = draw(gen, [(n,), (7,)], step, init)
+        gview.copy_(grads[0])
+        gp[0].grad = gview
+        gp[1].grad = grads[1].to(DEV)
+        gsnap = gbuf.clone()
+        step_and_check(f"unaligned_parameter_and_gradient[{k}-{j}-{n}]", opt, gp, twin, grads)
+        assert torch.equal(bits(gbuf), bits(gsnap)), "gradient buffer rewritten"
+        assert outside_equal(buf, snap, k, n), "parameter sentinels rewritten"
+    assert gp[0].data_ptr() == buf.data_ptr() + 4 * k
+
+
+def test_unaligned_moments():
+    """exp_avg and exp_avg_sq as views at odd offsets (state seeded before the
+    first step) under an aligned parameter and gradient: adam_kernel's scalar
+    path beside sumsq_kernel's vector one; the moment buffers' sentinels stay."""
+    from mtts.optim import FusedClipAdam
+    n = CHUNK + 5
+    gen = torch.Generator().manual_seed(0)
+    init = [torch.randn(n, generator=gen)]
+    gp = [torch.nn.Parameter(init[0].to(DEV))]
+    opt = FusedClipAdam(gp, lr=LR, betas=BETAS, eps=1e-8, weight_decay=0.01, max_grad_norm=1.0)
+    twin = Twin(init, LR, 0.01, 1.0)
+    mbuf, m = sliced(n, 1, P_SENTINEL)
+    vbuf, v = sliced(n, 3, P_SENTINEL)
+    m.zero_()
+    v.zero_()
+    opt.state[gp[0]] = {"step": torch.tensor(0.0), "exp_avg": m, "exp_avg_sq": v}
+    msnap, vsnap = mbuf.clone(), vbuf.clone()
+    for step in range(2):
+        grads = draw(gen, [(n,)], step, init)
+        gp[0].grad = grads[0].to(DEV)
+        assert gp[0].data_ptr() % 16 == 0 and gp[0].grad.data_ptr() % 16 == 0
+        step_and_check("unaligned_moments", opt, gp, twin, grads)
+        assert outside_equal(mbuf, msnap, 1, n) and outside_equal(vbuf, vsnap, 3, n), "moment sentinels rewritten"
+    st = opt.state[gp[0]]
+    assert st["exp_avg"].data_ptr() == mbuf.data_ptr() + 4 and st["exp_avg_sq"].data_ptr() == vbuf.data_ptr() + 12
+
+
+def test_moving_gradient_pointers():
+    """New gradient tensors between steps (the old ones kept alive, so the
+    addresses differ): the step follows the new gradients, and the descriptor
+    upload count rises by one per move and stays when only the values change."""
+    shapes = [(CHUNK + 1,), (7,), (33, 5)]
+    gen, init, gp, opt, twin = make(shapes)
+    keep, uploads = [], []
+    for step, move in enumerate([True, True, False, True]):
+        grads = draw(gen, shapes, step, init)
+        for p, g in zip(gp, grads):
+            if move:
+                keep.append(p.grad)
+                p.grad = g.to(DEV)
+            else:
+                p.grad.copy_(g)
+        step_and_check("moving_gradient_pointers", opt, gp, twin, grads)
+        (plan,) = opt._plans.values()
+        uploads.append(plan["uploads"])
+    assert uploads == [1, 2, 2, 3]
+    assert len({t.data_ptr() for t in keep if t is not None} | {p.grad.data_ptr() for p in gp}) == 9
+
+
+@pytest.mark.parametrize("max_norm", [1.0, None])
+def test_all_zero_gradients(max_norm):
+    """g = 0 without weight decay: coef = min(1, max_norm / 1e-6) = 1, the
+    moments stay 0 and p - step_size * (0 / eps) is p, bit for bit."""
+    shapes = [(CHUNK + 1,), (7,)]
+    gen, init, gp, opt, twin = make(shapes, wd=0.0, max_norm=max_norm)
+    snaps = [bits(p) for p in gp]
+    for step in range(2):
+        for p in gp:
+            p.grad = torch.zeros_like(p)
+        opt.step()
+        assert float(opt.last_grad_norm) == 0.0
+        for p, s0 in zip(gp, snaps):
+            assert torch.equal(bits(p), s0)
+            assert not opt.state[p]["exp_avg"].any() and not opt.state[p]["exp_avg_sq"].any()
+    assert float(opt.state[gp[0]]["step"]) == 2.0
+
+
+@pytest.mark.parametrize("max_norm", [1.0, None])
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_non_finite_gradient_as_torch(bad, max_norm):
+    """One NaN (inf) gradient element in the second step: which elements of the
+    parameters and moments turn NaN (inf) equals torch's own float32
+    clip_grad_norm_ + Adam on the CPU.  With clipping a NaN norm gives a NaN
+    coefficient (clamp(max_norm / (total + 1e-6), max=1) keeps NaN), so every
+    parameter turns NaN and last_grad_norm is NaN; an inf norm gives coef = 0
+    and NaN at that element alone (inf * 0).  Without clipping only that
+    element is touched.  Two steps: a third would compare torch's lerp
+    (inf + w * (g - inf) = NaN) with the kernel's b1 * inf + (1 - b1) * g = inf."""
+    shapes = [(CHUNK + 1,), (7,), (33, 5)]
+    gen, init, gp, opt, _ = make(shapes, max_norm=max_norm)
+    twin = Twin(init, LR, 0.01, max_norm, dtype=torch.float32)
+    for step in range(2):
+        grads = rand_grads(gen, shapes, step)
+        if step == 1:
+            grads[0][70] = bad
+        for p, g in zip(gp, grads):
+            p.grad = g.to(DEV)
+        opt.step()
+        _, total = twin.step(grads)
+        if total is not None:
+            norm = opt.last_grad_norm.cpu()
+            assert bool(torch.isnan(norm)) == bool(torch.isnan(total)) and bool(torch.isinf(norm)) == bool(
+                torch.isinf(total)), f"norm {float(norm)} vs torch's {float(total)}"
+            if step == 1 and bad != bad:
+                assert torch.isnan(norm)
+        rm, rv = twin.moments()
+        for i, p in enumerate(gp):
+            st = opt.state[p]
+            for name, a, b in (("p", p, twin.values()[i]), ("exp_avg", st["exp_avg"], rm[i]),
+                               ("exp_avg_sq", st["exp_avg_sq"], rv[i])):
+                a = a.detach().cpu()
+                assert torch.equal(torch.isnan(a), torch.isnan(b)), (
+                    f"step {step} {name}{i}: {int(torch.isnan(a).sum())} NaN vs torch's {int(torch.isnan(b).sum())}")
+                assert torch.equal(torch.isinf(a), torch.isinf(b)), f"step {step} {name}{i}: inf mask"
+    if max_norm is not None and bad != bad:
+        assert all(torch.isnan(p).all() for p in gp)
