@@ -259,6 +259,11 @@ int mtts_selective_state_update(const MttsStateUpdateArgs* a, void* stream);
  *                                     + beta[row / rows_per_group]
  * x/res/x_sum/y: (M, N) rows with row strides; gamma/beta: (G, N) with row
  * stride gb_stride (fp32 or dtype).  mean/rstd: (M) fp32, saved for bwd.
+ * gamma and beta have G = rows / rows_per_group rows: with gamma, rows must
+ * be a multiple of rows_per_group (MTTS_EINVAL otherwise, nothing launched).
+ * Rows, row strides and pointers that are all 16-byte aligned take 16-byte
+ * vector accesses; anything else (x_sum and, in the backward, dy, dx, dx_acc
+ * included) is read and written by element.
  * ------------------------------------------------------------------------ */
 typedef struct {
   int rows, cols, dtype, rows_per_group;

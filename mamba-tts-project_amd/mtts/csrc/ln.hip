@@ -258,15 +258,22 @@ static void launch_bwd(const MttsLNBwdArgs* a, int rb, float* part, hipStream_t 
                      rb, part);
 }
 
-// dispatch on (dtype, gamma dtype, cols)
+// 16-byte alignment of a pointer and of its row stride (in bytes)
+static bool al16(const void* p, int64_t rs_bytes) { return (uintptr_t)p % 16 == 0 && rs_bytes % 16 == 0; }
+
+// dispatch on (dtype, gamma dtype, cols).  The 16-byte vector path needs every
+// tensor the kernel touches with uint4 accesses aligned: x, y, res, gamma and
+// beta are looked at here; `more_ok` carries the caller's own (the forward's
+// x_sum, the backward's dy, dx, dx_acc and the fp32 w / b).  Anything
+// misaligned takes the element (VEC = 1) path.
 template <template <typename, typename, int, int> class F, typename... Args>
-static int dispatch_ln(const MttsLNArgs* a, Args... args) {
+static int dispatch_ln(const MttsLNArgs* a, bool more_ok, Args... args) {
   const int n = a->cols;
   auto go = [&](auto tag_t, auto tag_g) -> int {
     using T = typename decltype(tag_t)::type;
     using TG = typename decltype(tag_g)::type;
     constexpr int VEC = 16 / sizeof(T);
-    const bool vec_ok = n % (64 * VEC) == 0 && (a->x_rs * (int64_t)sizeof(T)) % 16 == 0 &&
+    const bool vec_ok = more_ok && n % (64 * VEC) == 0 && (a->x_rs * (int64_t)sizeof(T)) % 16 == 0 &&
                         (a->y_rs * (int64_t)sizeof(T)) % 16 == 0 && (uintptr_t)a->x % 16 == 0 &&
                         (uintptr_t)a->y % 16 == 0 &&
                         (!a->res || ((uintptr_t)a->res % 16 == 0 && (a->res_rs * (int64_t)sizeof(T)) % 16 == 0)) &&
@@ -318,10 +325,15 @@ struct BwdRunner {
 };
 
 static int check_ln(const MttsLNArgs* a) {
-  MTTS_CHECK(a && a->x && a->w && a->b && a->y && a->mean && a->rstd, "layernorm: null tensor");
+  MTTS_CHECK(a && a->w && a->b, "layernorm: null tensor");
   MTTS_CHECK(a->rows >= 0 && a->cols > 0, "layernorm: bad sizes");
+  // an empty tensor has no storage: the per-row pointers may be null when there are no rows
+  MTTS_CHECK(a->rows == 0 || (a->x && a->y && a->mean && a->rstd), "layernorm: null tensor");
   MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "layernorm: bad dtype");
   MTTS_CHECK(!a->gamma || (a->beta && a->rows_per_group > 0), "layernorm: FiLM needs beta and rows_per_group");
+  // gamma / beta hold rows / rows_per_group rows: a ragged last group would index one past them
+  MTTS_CHECK(!a->gamma || a->rows % a->rows_per_group == 0,
+             "layernorm: rows=%d is not a multiple of rows_per_group=%d", a->rows, a->rows_per_group);
   return MTTS_OK;
 }
 
@@ -333,7 +345,9 @@ extern "C" int mtts_layernorm_fwd(const MttsLNArgs* a, void* stream) {
   int rc = check_ln(a);
   if (rc) return rc;
   if (a->rows == 0) return MTTS_OK;
-  rc = dispatch_ln<FwdRunner>(a, (hipStream_t)stream);
+  const int64_t es = a->dtype == MTTS_F32 ? 4 : 2;
+  const bool sum_ok = !(a->res && a->x_sum) || al16(a->x_sum, a->xsum_rs * es);
+  rc = dispatch_ln<FwdRunner>(a, sum_ok, (hipStream_t)stream);
   if (rc) return rc;
   MTTS_LAUNCH_CHECK("layernorm_fwd");
   return MTTS_OK;
@@ -353,7 +367,7 @@ extern "C" int mtts_layernorm_bwd(const MttsLNBwdArgs* a, void* stream) {
   MTTS_CHECK(a, "layernorm_bwd: null args");
   int rc = check_ln(&a->f);
   if (rc) return rc;
-  MTTS_CHECK(a->dy && a->dx && a->dw && a->db && a->workspace, "layernorm_bwd: null tensor");
+  MTTS_CHECK(a->dw && a->db && (a->f.rows == 0 || (a->dy && a->dx && a->workspace)), "layernorm_bwd: null tensor");
   MTTS_CHECK(!a->f.gamma || (a->dgamma && a->dbeta), "layernorm_bwd: FiLM needs dgamma/dbeta");
   const MttsLNArgs& f = a->f;
   hipStream_t st = (hipStream_t)stream;
@@ -366,7 +380,14 @@ extern "C" int mtts_layernorm_bwd(const MttsLNBwdArgs* a, void* stream) {
   }
   const int rb = ln_rb(&f);
   float* part = (float*)a->workspace;
-  rc = dispatch_ln<BwdRunner>(&f, a, rb, part, st);
+  // the kernel reads f.x (or f.x_sum), dy and dx_acc and writes dx with 16-byte vectors,
+  // and an fp32 row's w / b as well
+  const int64_t es = f.dtype == MTTS_F32 ? 4 : 2;
+  const bool src_sum = f.res && f.x_sum;
+  const bool grads_ok = al16(a->dy, a->dy_rs * es) && al16(a->dx, a->dx_rs * es) &&
+                        (!a->dx_acc || al16(a->dx_acc, a->dxacc_rs * es)) &&
+                        (!src_sum || al16(f.x_sum, f.xsum_rs * es)) && al16(f.w, 0) && al16(f.b, 0);
+  rc = dispatch_ln<BwdRunner>(&f, grads_ok, a, rb, part, st);
   if (rc) return rc;
   MTTS_LAUNCH_CHECK("layernorm_bwd");
   const int nblk = (f.rows + rb - 1) / rb;

@@ -341,6 +341,8 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
 def _rows(t):
     """(..., N) with last stride 1 -> (rows, row_stride)."""
     n = t.shape[-1]
+    if t.numel() == 0:      # no rows: whatever strides an empty view carries
+        return 0, n
     if t.stride(-1) != 1:
         raise ValueError("layernorm: last stride must be 1")
     rows = t.numel() // n
@@ -352,6 +354,16 @@ def _rows(t):
         if t.shape[d] > 1 and t.stride(d) != st * _prod(t.shape[d + 1:-1]):
             raise ValueError("layernorm: leading dims must be collapsible")
     return rows, st
+
+
+def _as_rows(t):
+    """A gradient as autograd hands it over (an expanded or sliced view, say):
+    itself when it is rows with one stride, a contiguous copy otherwise."""
+    try:
+        _rows(t)
+    except ValueError:
+        return t.contiguous()
+    return t
 
 
 def _prod(s):
@@ -377,6 +389,21 @@ def _ln_args(x, w, b, eps, res, x_sum, gamma, beta, rows_per_group, y, mean, rst
     return a
 
 
+def _check_film(x, gamma, beta, rows_per_group):
+    """gamma / beta: (G, N) with G * rows_per_group rows of x -- the kernels
+    index them by row // rows_per_group and do not look at G."""
+    cols = x.shape[-1]
+    rows = x.numel() // cols
+    if beta is None or beta.shape != gamma.shape:
+        raise ValueError(f"layernorm: beta {None if beta is None else tuple(beta.shape)} must have gamma's "
+                         f"shape {tuple(gamma.shape)}")
+    if gamma.dim() != 2 or gamma.shape[1] != cols:
+        raise ValueError(f"layernorm: gamma / beta must be (G, {cols}), got {tuple(gamma.shape)}")
+    if rows_per_group <= 0 or gamma.shape[0] * rows_per_group != rows:
+        raise ValueError(f"layernorm: {gamma.shape[0]} FiLM groups of rows_per_group={rows_per_group} rows "
+                         f"do not make up the {rows} rows of x")
+
+
 def layernorm_fwd(x, w, b, eps=1e-5, res=None, gamma=None, beta=None, rows_per_group=1, want_sum=True):
     """y = LN(x [+ res]) * w + b [then gamma*y + beta per row group].
     Returns (y, mean, rstd, x_sum | None)."""
@@ -389,6 +416,7 @@ def layernorm_fwd(x, w, b, eps=1e-5, res=None, gamma=None, beta=None, rows_per_g
         res = res.to(x.dtype)
     w, b = _f32c(w), _f32c(b)
     if gamma is not None:
+        _check_film(x, gamma, beta, rows_per_group)
         gamma = gamma if gamma.stride(-1) == 1 else gamma.contiguous()
         beta = beta if beta.stride(-1) == 1 else beta.contiguous()
         if beta.stride(0) != gamma.stride(0):
@@ -409,7 +437,7 @@ def layernorm_bwd(xn, w, b, eps, gamma, beta, rows_per_group, mean, rstd, dy, dx
     dgb: an fp32 (G, 2N) buffer receiving dgamma | dbeta side by side (then
     returned as the two halves); dx_colsum: an fp32 (N) buffer receiving the
     column sums of dx (the bias gradient of the linear that produced x)."""
-    dy = dy if dy.stride(-1) == 1 else dy.contiguous()
+    dy = _as_rows(dy)
     if dy.dtype != xn.dtype:
         dy = dy.to(xn.dtype)
     w, b = _f32c(w), _f32c(b)
@@ -430,7 +458,7 @@ def layernorm_bwd(xn, w, b, eps, gamma, beta, rows_per_group, mean, rstd, dy, dx
     bb.f = _ln_args(xn, w, b, eps, None, None, gamma, beta, rows_per_group, xn, mean, rstd)
     bb.dy, bb.dy_rs = dy.data_ptr(), _rows(dy)[1]
     if dx_acc is not None:
-        dx_acc = dx_acc if dx_acc.stride(-1) == 1 else dx_acc.contiguous()
+        dx_acc = _as_rows(dx_acc)
         if dx_acc.dtype != xn.dtype:
             dx_acc = dx_acc.to(xn.dtype)
         bb.dx_acc, bb.dxacc_rs = dx_acc.data_ptr(), _rows(dx_acc)[1]
@@ -455,6 +483,8 @@ class LayerNormFn(torch.autograd.Function):
     def forward(ctx, x, res, w, b, gamma, beta, eps, rows_per_group, film, colsum_slot):
         if film is not None:
             n = x.shape[-1]
+            if film.dim() != 2 or film.shape[1] != 2 * n:
+                raise ValueError(f"layernorm: film must be (G, {2 * n}) = gamma | beta, got {tuple(film.shape)}")
             gamma, beta = film[:, :n], film[:, n:]
         y, mean, rstd, x_sum = layernorm_fwd(x, w, b, eps, res, gamma, beta, rows_per_group)
         xn = x_sum if res is not None else x
