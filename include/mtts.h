@@ -37,7 +37,10 @@ extern "C" {
  * behaviour), MttsSampleArgs.reserved_ named pos_rows (0 = the old behaviour,
  * same offset and size) and one new symbol, mtts_embed_sum_at.  A caller
  * built against the earlier header must zero the appended fields; a binding
- * that needs the additions checks that mtts_embed_sum_at resolves. */
+ * that needs the additions checks that mtts_embed_sum_at resolves.  The
+ * per-row token sampler (MttsSampleRowsArgs, mtts_sample_tokens_rows) is
+ * additive in the same way: MttsSampleArgs and mtts_sample_tokens are
+ * untouched, and a binding that needs it checks that the symbol resolves. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -887,6 +890,72 @@ typedef struct {
 } MttsSampleArgs;
 
 int mtts_sample_tokens(const MttsSampleArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Per-row token sampler (an addition within ABI 15; a binding that needs it
+ * checks that the symbol resolves).  The sampler above with its controls read
+ * per row from device memory at run time, so rows of one launch -- and
+ * replays of one captured launch -- may differ in every one of them, and with
+ * a random stream that belongs to the row's request, not to its place:
+ *   temperature[r]: !(T > 0) is greedy (argmax, lowest index, no random numbers);
+ *   top_k[r]:       <= 0 or >= vocab is off;
+ *   top_p[r]:       anything outside (0, 1) is off;
+ *   draw:           as above, with h = splitmix64-finalizer(seed[r] +
+ *                   (draw[r] * vocab + v) * 0x9E3779B97F4A7C15) (64-bit
+ *                   wrapping): a function of (seed[r], draw[r], v) alone, not
+ *                   of the row index, the row count or *step.  draw[r] grows by
+ *                   one whenever row r emits a token of its own (greedy rows
+ *                   included); a finished row draws nothing and keeps it.
+ *   penalty[r] = t: off for !(t > 0), t == 1 and t == inf.  Otherwise, with
+ *                   col = *step - step0 and n = min(window, draw[r], col), every
+ *                   id of history[r, col - n .. col) that lies in [0, vocab)
+ *                   (others, and columns outside [0, hist_cols), are skipped)
+ *                   has x_v replaced, once however often it occurs, by
+ *                   x_v / t for x_v > 0 and x_v * t otherwise: correctly rounded
+ *                   fp32, applied after NaN -> -inf (-inf and 0 stay).  Maximum,
+ *                   top-k, top-p and the draw all see the penalised x.
+ *   max_length[r]:  after a row emits a token and length[r] has grown,
+ *                   length[r] >= max_length[r] finishes the row (the token is
+ *                   emitted; pad_id follows).  eos_id works as above.
+ * Everything else -- logits, bias, tokens, history, finished, length,
+ * unfinished, step, step0, pos, pos_rows, advance -- is as in MttsSampleArgs;
+ * the shared *step still selects the history column.
+ * ------------------------------------------------------------------------ */
+#define MTTS_SAMPLE_WINDOW_MAX 256
+
+typedef struct {
+  int rows, vocab;           /* rows >= 1, 1 <= vocab <= 2^24 */
+  int dtype;                 /* MTTS_F32 / MTTS_BF16 (logits) */
+  int window;                /* 0..MTTS_SAMPLE_WINDOW_MAX; > 0 needs `history` */
+  int64_t ld;                /* logits row stride (elements), >= vocab */
+  const void* logits;
+  const float* bias;         /* optional (vocab,) or, with bias_ld > 0, (rows, vocab) */
+  int64_t bias_ld;
+  const float* temperature;  /* (rows,) device */
+  const int* top_k;          /* (rows,) device */
+  const float* top_p;        /* (rows,) device */
+  const int64_t* seed;       /* (rows,) device */
+  int* draw;                 /* (rows,) device, in and out */
+  const float* penalty;      /* optional (rows,) device */
+  const int64_t* max_length; /* optional (rows,) device; needs `finished` and `length` */
+  int* step;                 /* device; NULL: 0 (and no advance) */
+  int advance;
+  int step0;
+  int* pos;
+  int64_t* tokens;           /* out */
+  int64_t tok_stride;
+  int64_t* history;          /* optional; the penalty window reads it */
+  int64_t hist_ld;
+  int hist_cols;
+  int eos_id;                /* < 0: none */
+  int pad_id;
+  int pos_rows;
+  int* finished;             /* optional (rows,) */
+  int64_t* length;           /* optional (rows,) */
+  int* unfinished;           /* optional (needs `finished`) */
+} MttsSampleRowsArgs;
+
+int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream);
 
 #ifdef __cplusplus
 }

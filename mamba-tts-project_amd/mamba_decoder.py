@@ -347,7 +347,8 @@ class MambaTTSDecoder(nn.Module):
     @torch.no_grad()
     def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, prompt_lengths=None, start_token=0,
                  text_mask=None, ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0,
-                 logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32):
+                 logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32, repetition_penalty=None,
+                 repetition_window=64):
         """Generate up to `max_new_tokens` codec tokens on the device
         (mtts/decode.py DecodeEngine.generate): the decode_step loop with the
         draw (temperature, top-k, top-p, reproducible from `seed`) in the HIP
@@ -367,7 +368,24 @@ class MambaTTSDecoder(nn.Module):
         on, and generation stops once every row has (polled every
         `check_every` steps).
 
-        Returns tokens (B, n) int64 with n <= max_new_tokens and lengths (B,)
+        Per-request sampling: temperature, top_k, top_p, seed and
+        max_new_tokens each take a scalar or one value per row ((B,) list or
+        tensor), so requests with different settings share a batch (and one
+        captured graph: the per-row values are device data).  Row b then draws
+        from its own stream, a function of (seed_b, number of tokens row b has
+        drawn, token id) only -- the same request with the same seed gives the
+        same tokens in any row of any batch; a scalar seed is expanded with
+        mtts.ops.row_seeds(seed, B).  A row stops at its own max_new_tokens
+        and is padded with pad_id.
+        repetition_penalty (scalar or (B,), > 0; None or 1.0: off): a logit
+        of a token that occurs among the row's last `repetition_window`
+        (0..256) generated tokens is divided by it when positive and
+        multiplied by it otherwise, once per distinct token.  The window
+        covers GENERATED tokens only: prompt tokens are not penalised.
+        With every one of these a scalar and no penalty the call is the
+        scalar path, unchanged.
+
+        Returns tokens (B, n) int64 with n <= max(max_new_tokens) and lengths (B,)
         int64 (tokens up to and including a row's eos_id)."""
         if not self.decode_mode:
             raise RuntimeError("generate runs on the decode engine: set decode_mode to 'graph' or 'eager'")
@@ -380,4 +398,5 @@ class MambaTTSDecoder(nn.Module):
                                      prompt_lengths=prompt_lengths, start_token=start_token, text_mask=text_mask, ref_hidden=ref_hidden,
                                      ref_mask=ref_mask, temperature=temperature, top_k=top_k, top_p=top_p,
                                      logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
-                                     check_every=check_every)
+                                     check_every=check_every, repetition_penalty=repetition_penalty,
+                                     repetition_window=repetition_window)

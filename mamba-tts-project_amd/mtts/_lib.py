@@ -104,6 +104,15 @@ class SampleArgs(C.Structure):
                 ("pos_rows", i32), ("finished", vp), ("length", vp), ("unfinished", vp)]
 
 
+class SampleRowsArgs(C.Structure):
+    _fields_ = [("rows", i32), ("vocab", i32), ("dtype", i32), ("window", i32), ("ld", i64), ("logits", vp),
+                ("bias", vp), ("bias_ld", i64), ("temperature", vp), ("top_k", vp), ("top_p", vp), ("seed", vp),
+                ("draw", vp), ("penalty", vp), ("max_length", vp), ("step", vp), ("advance", i32), ("step0", i32),
+                ("pos", vp), ("tokens", vp), ("tok_stride", i64), ("history", vp), ("hist_ld", i64),
+                ("hist_cols", i32), ("eos_id", i32), ("pad_id", i32), ("pos_rows", i32), ("finished", vp),
+                ("length", vp), ("unfinished", vp)]
+
+
 class RowMap(C.Structure):
     _fields_ = [("ptr", vp), ("seg_rows", i64), ("seg_stride", i64), ("row_stride", i64), ("halo_c", i32),
                 ("halo_p", i32)]
@@ -214,6 +223,7 @@ _SIGS = {
     "mtts_length_regulate_bwd": ([vp, i32, i32, i32, i32, i64, i64, vp, i64, i32, vp, i64, i64, vp], i32),
     "mtts_dropout": ([C.POINTER(DropoutArgs), vp], i32),
     "mtts_sample_tokens": ([C.POINTER(SampleArgs), vp], i32),
+    "mtts_sample_tokens_rows": ([C.POINTER(SampleRowsArgs), vp], i32),
 }
 
 _lib = None
@@ -230,6 +240,7 @@ def lib():
         # ABI 15 grew by additions only, so a library built before them reports
         # the same version: the added symbols tell them apart
         for sym, what in (("mtts_embed_sum_at", "ragged prompts"),
+                          ("mtts_sample_tokens_rows", "per-row sampling"),
                           ("mtts_gemm_grouped_rounds", "round-filling weight gradients")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "

@@ -28,7 +28,16 @@
 // The step counter is read by every workgroup and advanced by a one-workgroup
 // launch behind the sampler (which also recounts the unfinished rows), so
 // nothing depends on the order in which workgroups run and there are no
-// atomics.
+// atomics in global memory.
+//
+// The same kernel has a per-row form (mtts_sample_tokens_rows): temperature,
+// top-k, top-p, seed, draw count, repetition penalty and length cap are read
+// per row from device arrays, and the Gumbel counter is the row's own
+// (seed_r, draw_r, v).  The penalty window (<= 256 history columns) becomes a
+// small LDS set before the first pass, and load() tests membership, so the
+// LDS-staged row is penalised as it is staged and a longer row on every
+// re-read; every pass downstream sees the penalised value.  The scalar form
+// instantiates none of this.
 #include "common.h"
 
 #include <math.h>
@@ -116,16 +125,49 @@ __device__ __forceinline__ float gumbel(uint32_t n) {
 
 struct SampleParams {
   MttsSampleArgs a;
+  static constexpr bool kRows = false;
+};
+struct SampleRowsParams {   // the per-row form: controls read from device arrays (mtts_sample_tokens_rows)
+  MttsSampleRowsArgs a;
+  static constexpr bool kRows = true;
 };
 
-template <typename T, int NW>
-__global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm) {
+// The per-row form's penalty window as a set: open addressing over kWinSlots
+// LDS words (-1 = empty).  At most MTTS_SAMPLE_WINDOW_MAX = kWinSlots / 2
+// distinct ids go in, so an empty word always ends a probe.  Which word an id
+// lands in depends on the order of the inserts; whether it is found does not.
+constexpr int kWinSlots = 512;
+static_assert(kWinSlots >= 2 * MTTS_SAMPLE_WINDOW_MAX && (kWinSlots & (kWinSlots - 1)) == 0, "window set too small");
+__device__ __forceinline__ uint32_t win_hash(int id) { return ((uint32_t)id * 0x9E3779B1u) >> 23; }   // 9 bits
+__device__ __forceinline__ void win_insert(int* tab, int id) {
+  uint32_t h = win_hash(id);
+  for (int i = 0; i < kWinSlots; ++i) {
+    const int old = atomicCAS(&tab[h], -1, id);
+    if (old == -1 || old == id) return;
+    h = (h + 1) & (kWinSlots - 1);
+  }
+}
+__device__ __forceinline__ bool win_has(const int* tab, int id) {
+  uint32_t h = win_hash(id);
+  for (int i = 0; i < kWinSlots; ++i) {
+    const int e = tab[h];
+    if (e == id) return true;
+    if (e == -1) return false;
+    h = (h + 1) & (kWinSlots - 1);
+  }
+  return false;
+}
+
+template <typename T, int NW, typename P>
+__global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   constexpr int kThreads = NW * 64;
   constexpr int kCache = NW == 1 ? kSampleWaveV : kSampleCache;
-  const MttsSampleArgs& p = prm.a;
+  constexpr bool kRows = P::kRows;
+  const auto& p = prm.a;
   __shared__ float xs[kCache];
   __shared__ float es[kCache];
   __shared__ uint64_t slots[2][4];
+  __shared__ int wtab[kRows ? kWinSlots : 1];
   int phase = 0;
   const int row = blockIdx.x, tid = threadIdx.x, V = p.vocab;
   const int step = p.step ? *p.step : 0;
@@ -133,6 +175,25 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
   int64_t* const hist = (p.history && col >= 0 && col < p.hist_cols) ? p.history + (int64_t)row * p.hist_ld + col
                                                                      : nullptr;
   int64_t* const tok_out = p.tokens + (int64_t)row * p.tok_stride;
+  // this row's controls: kernel arguments, or (per-row form) device arrays with
+  // the header's effective rules, so that no value can index or loop out of range.
+  // All read here, the length cap included, in one batch of loads.
+  float T_, top_p_, theta = 1.f;
+  int top_k_, drawn = 0;
+  int64_t cap = INT64_MAX;
+  if constexpr (kRows) {
+    T_ = p.temperature[row];
+    top_k_ = p.top_k[row];
+    top_p_ = p.top_p[row];
+    drawn = p.draw[row];
+    if (p.penalty) theta = p.penalty[row];
+    if (p.max_length) cap = p.max_length[row];
+    if (!(top_p_ > 0.f && top_p_ < 1.f)) top_p_ = 1.f;
+  } else {
+    T_ = p.temperature;
+    top_k_ = p.top_k;
+    top_p_ = p.top_p;
+  }
   if (p.finished && p.finished[row] != 0) {   // past its end of sequence: pad, length frozen
     if (tid == 0) {
       *tok_out = p.pad_id;
@@ -143,10 +204,32 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
   const T* __restrict__ lg = reinterpret_cast<const T*>(p.logits) + (int64_t)row * p.ld;
   const float* __restrict__ bias = p.bias ? p.bias + (int64_t)row * p.bias_ld : nullptr;
   const bool cached = V <= kCache;
+  bool pen = false;   // the repetition penalty applies to this row (uniform in the workgroup)
+  if constexpr (kRows) {
+    int n = p.window < MTTS_SAMPLE_WINDOW_MAX ? p.window : MTTS_SAMPLE_WINDOW_MAX;
+    n = n < drawn ? n : drawn;
+    n = n < col ? n : col;
+    pen = theta > 0.f && theta != 1.f && theta < INFINITY && n > 0 && p.history != nullptr;
+    if (pen) {
+      for (int i = tid; i < kWinSlots; i += kThreads) wtab[i] = -1;
+      block_sync();
+      const int64_t* const hrow = p.history + (int64_t)row * p.hist_ld;
+      for (int j = tid; j < n; j += kThreads) {
+        const int c = col - n + j;                     // >= 0: n <= col
+        if (c >= p.hist_cols) continue;
+        const int64_t id = hrow[c];
+        if (id >= 0 && id < (int64_t)V) win_insert(wtab, (int)id);   // checked before it indexes anything
+      }
+      block_sync();
+    }
+  }
   auto load = [&](int v) {
     float x = ldf(lg + v);
     if (bias) x += bias[v];
     if (!(x == x)) x = -INFINITY;   // NaN counts as -inf
+    if constexpr (kRows) {
+      if (pen && win_has(wtab, v)) x = x > 0.f ? __fdiv_rn(x, theta) : __fmul_rn(x, theta);
+    }
     if (x == 0.f) x = 0.f;          // -0 and +0 tie: one key
     return x;
   };
@@ -166,12 +249,11 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
   int64_t token = (int64_t)(uint32_t)~(uint32_t)best;
   if (m == -INFINITY) {
     token = p.pad_id;               // no finite candidate
-  } else if (p.temperature > 0.f && m < INFINITY) {
-    const float T_ = p.temperature;
+  } else if (T_ > 0.f && m < INFINITY) {
     const float invT = 1.f / T_;
     uint32_t K = 0;
-    if (p.top_k > 0 && p.top_k < V) {
-      const uint32_t k = (uint32_t)p.top_k;
+    if (top_k_ > 0 && top_k_ < V) {
+      const uint32_t k = (uint32_t)top_k_;
       uint32_t lo = 0, hi = kmax;
       while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -182,7 +264,7 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
       }
       K = lo;
     }
-    if (p.top_p < 1.f) {
+    if (top_p_ < 1.f) {
       // e_v = exp((x_v - m) / T) over the top-k survivors (0 elsewhere; exp(-inf) = 0)
       auto E = [&](int v, float x) { return fkey(x) >= K ? expf((x - m) * invT) : 0.f; };
       float z = 0.f;
@@ -192,7 +274,7 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
         z += e;
       }
       z = block_sum<NW>(z, slots, phase);
-      const float target = p.top_p * z;
+      const float target = top_p_ * z;
       uint32_t lo = K, hi = kmax;
       while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -208,8 +290,14 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
       K = lo;
     }
     // Gumbel-max draw over the kept set
-    const uint64_t seed = p.seed ? (uint64_t)*p.seed : 0ull;
-    const uint64_t c0 = ((uint64_t)(int64_t)step * (uint64_t)p.rows + (uint64_t)row) * (uint64_t)V;
+    uint64_t seed, c0;
+    if constexpr (kRows) {   // the row's own stream: (seed_r, draw_r, v), wherever the row sits
+      seed = (uint64_t)p.seed[row];
+      c0 = (uint64_t)(int64_t)drawn * (uint64_t)V;
+    } else {
+      seed = p.seed ? (uint64_t)*p.seed : 0ull;
+      c0 = ((uint64_t)(int64_t)step * (uint64_t)p.rows + (uint64_t)row) * (uint64_t)V;
+    }
     uint64_t pick = 0;
     for (int v = tid; v < V; v += kThreads) {
       const float x = X(v);
@@ -226,7 +314,16 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const SampleParams prm)
   if (tid == 0) {
     *tok_out = token;
     if (hist) *hist = token;
-    if (p.length) p.length[row] += 1;
+    if constexpr (kRows) {
+      p.draw[row] = drawn + 1;
+      if (p.length) {
+        const int64_t len = p.length[row] + 1;
+        p.length[row] = len;
+        if (p.finished && len >= cap) p.finished[row] = 1;
+      }
+    } else {
+      if (p.length) p.length[row] += 1;
+    }
     if (p.finished && p.eos_id >= 0 && token == p.eos_id) p.finished[row] = 1;
   }
 }
@@ -280,17 +377,62 @@ extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
   prm.a = *a;
   const bool f32 = a->dtype == MTTS_F32;
   if (a->vocab <= kSampleWaveV) {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1>), dim3(a->rows), dim3(64), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1>), dim3(a->rows), dim3(64), 0, st, prm);
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleParams>), dim3(a->rows), dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleParams>), dim3(a->rows), dim3(64), 0, st, prm);
   } else {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 4>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 4>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    if (f32)
+      hipLaunchKernelGGL((sample_kernel<float, 4, SampleParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    else
+      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
   }
   MTTS_LAUNCH_CHECK("sample_tokens");
   if (a->advance || a->unfinished) {
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
                        a->rows, a->unfinished, a->advance, a->pos_rows);
     MTTS_LAUNCH_CHECK("sample_tokens (advance)");
+  }
+  return MTTS_OK;
+}
+
+extern "C" int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream) {
+  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens_rows: null pointer");
+  MTTS_CHECK(a->temperature && a->top_k && a->top_p && a->seed && a->draw,
+             "sample_tokens_rows: temperature, top_k, top_p, seed and draw are required");
+  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens_rows: dtype must be f32 or bf16");
+  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24),
+             "sample_tokens_rows: rows=%d vocab=%d out of range", a->rows, a->vocab);
+  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
+             "sample_tokens_rows: row stride below vocab");
+  MTTS_CHECK(a->window >= 0 && a->window <= MTTS_SAMPLE_WINDOW_MAX, "sample_tokens_rows: window=%d outside [0, %d]",
+             a->window, MTTS_SAMPLE_WINDOW_MAX);
+  MTTS_CHECK(a->window == 0 || a->history, "sample_tokens_rows: window=%d needs history", a->window);
+  MTTS_CHECK(!a->max_length || (a->finished && a->length), "sample_tokens_rows: max_length needs finished and length");
+  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
+             "sample_tokens_rows: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
+  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols),
+             "sample_tokens_rows: bad history shape");
+  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens_rows: unfinished needs finished");
+  MTTS_CHECK(!a->advance || a->step, "sample_tokens_rows: advance needs step");
+  MTTS_CHECK(a->pos_rows >= 0, "sample_tokens_rows: pos_rows=%d must be >= 0", a->pos_rows);
+  hipStream_t st = (hipStream_t)stream;
+  SampleRowsParams prm;
+  prm.a = *a;
+  const bool f32 = a->dtype == MTTS_F32;
+  if (a->vocab <= kSampleWaveV) {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleRowsParams>), dim3(a->rows), dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleRowsParams>), dim3(a->rows), dim3(64), 0, st, prm);
+  } else {
+    if (f32)
+      hipLaunchKernelGGL((sample_kernel<float, 4, SampleRowsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    else
+      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleRowsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st,
+                         prm);
+  }
+  MTTS_LAUNCH_CHECK("sample_tokens_rows");
+  if (a->advance || a->unfinished) {
+    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
+                       a->rows, a->unfinished, a->advance, a->pos_rows);
+    MTTS_LAUNCH_CHECK("sample_tokens_rows (advance)");
   }
   return MTTS_OK;
 }

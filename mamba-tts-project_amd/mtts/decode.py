@@ -27,6 +27,9 @@ Engine path (inference only: torch.no_grad, HIP tensors):
     the scan path.  Positions are per row ((B,) device buffers), so a ragged,
     right-padded prompt batch (prompt_lengths) runs the same captured graph:
     the prefill stops every row's scan / conv state at its own length.
+    Per-request sampling (per-row temperature / top-k / top-p / seed / length
+    cap, repetition penalty) goes through the per-row sampler, whose controls
+    are (B,) device buffers too: one graph serves every mix of settings.
 Numerics are those of the eager module path (tests/test_gpu_modules.py).
 Call `reset()` after modifying weights in place between decode steps.
 """
@@ -56,6 +59,38 @@ def _same_ctx(refs, versions, tensors):
         if t is not None and t._version != v:
             return False
     return True
+
+
+def _is_scalar(v):
+    """A plain number or a 0-d tensor / array (generate's per-row arguments)."""
+    if isinstance(v, (list, tuple)):
+        return False
+    shape = getattr(v, "shape", None)
+    return shape is None or len(shape) == 0
+
+
+def _per_row(name, v, B, integer):
+    """`v`, a scalar or (B,) list / tensor, as a (B,) CPU tensor: float64, or
+    int64 when `integer` (seeds wrapped into the int64 range, as the scalar
+    path does).  Raises ValueError naming the argument."""
+    if isinstance(v, torch.Tensor):
+        if integer and (v.dtype.is_floating_point or v.dtype == torch.bool):
+            raise ValueError(f"generate: {name} must hold integers")
+        v = v.detach().cpu().tolist()              # the one host copy of a device tensor
+    elif hasattr(v, "tolist"):
+        v = v.tolist()
+    vals = list(v) if isinstance(v, (list, tuple)) else [v] * B
+    if len(vals) != B:
+        raise ValueError(f"generate: {name} must be a scalar or hold one value per row ({B}), got {len(vals)}")
+    try:
+        if integer:
+            if any(isinstance(x, float) and x != int(x) for x in vals):
+                raise ValueError
+            vals = [(int(x) + (1 << 63)) % (1 << 64) - (1 << 63) if name == "seed" else int(x) for x in vals]
+            return torch.tensor(vals, dtype=torch.int64)
+        return torch.tensor([float(x) for x in vals], dtype=torch.float64)
+    except (TypeError, ValueError, OverflowError, RuntimeError):
+        raise ValueError(f"generate: {name} must hold {'integers' if integer else 'numbers'}") from None
 
 
 def _proj_blas(x, w, b=None, act=None):
@@ -487,10 +522,18 @@ class DecodeEngine:
     def _gen_buffers(self, B, V, dev):
         """Device-resident generation state, made once per context (before any
         capture): seed / step counters, the token history, end-of-sequence
-        bookkeeping, the logit bias and pinned slots for the early-stop polls."""
+        bookkeeping, the logit bias, pinned slots for the early-stop polls and
+        the per-row sampler's controls (filled per call, read at run time)."""
         if self.gen is None:
             cap = self.m.pos_embed.num_embeddings
             self.gen = dict(
+                temperature=torch.zeros(B, dtype=torch.float32, device=dev),
+                top_k=torch.zeros(B, dtype=torch.int32, device=dev),
+                top_p=torch.ones(B, dtype=torch.float32, device=dev),
+                row_seed=torch.zeros(B, dtype=torch.int64, device=dev),
+                draw=torch.zeros(B, dtype=torch.int32, device=dev),
+                penalty=torch.ones(B, dtype=torch.float32, device=dev),
+                max_length=torch.full((B,), cap, dtype=torch.int64, device=dev),
                 seed=torch.zeros(1, dtype=torch.int64, device=dev), step=torch.zeros(1, dtype=torch.int32, device=dev),
                 hist=torch.zeros(B, cap, dtype=torch.int64, device=dev),
                 finished=torch.zeros(B, dtype=torch.int32, device=dev),
@@ -499,6 +542,35 @@ class DecodeEngine:
                 bias=torch.zeros(B, V, dtype=torch.float32, device=dev),
                 host=torch.zeros(cap, dtype=torch.int32, pin_memory=True))
         return self.gen
+
+    @staticmethod
+    def _row_controls(B, temperature, top_k, top_p, seed, max_new_tokens, penalty, window):
+        """generate's per-row arguments, scalars broadcast, checked on the host
+        (ValueError names the argument) and returned as (B,) CPU tensors under
+        the names of the device buffers they fill, plus the window."""
+        T = _per_row("temperature", temperature, B, False)
+        k = _per_row("top_k", top_k, B, True)
+        p = _per_row("top_p", top_p, B, False)
+        caps = _per_row("max_new_tokens", max_new_tokens, B, True)
+        th = _per_row("repetition_penalty", 1.0 if penalty is None else penalty, B, False)
+        if _is_scalar(seed):
+            s = torch.tensor(ops.row_seeds(int(seed), B), dtype=torch.int64)
+        else:
+            s = _per_row("seed", seed, B, True)
+        if not bool((torch.isfinite(T) & (T >= 0)).all()):
+            raise ValueError("generate: temperature must be finite and >= 0 in every row")
+        if not bool(((k >= 0) & (k < (1 << 31))).all()):
+            raise ValueError("generate: top_k must be >= 0 in every row")
+        if not bool(((p > 0) & (p <= 1)).all()):
+            raise ValueError("generate: top_p must be in (0, 1] in every row")
+        if not bool((torch.isfinite(th) & (th > 0)).all()):
+            raise ValueError("generate: repetition_penalty must be finite and > 0 in every row")
+        if not bool((caps >= 1).all()):
+            raise ValueError("generate: max_new_tokens must be >= 1 in every row")
+        if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window <= 256:
+            raise ValueError("generate: repetition_window must be an integer in [0, 256]")
+        return dict(temperature=T.float(), top_k=k.int(), top_p=p.float(), row_seed=s, penalty=th.float(),
+                    max_length=caps, window=window)
 
     def _prefill(self, prompt, conds, lens=None):
         """The whole prompt through the parallel (scan) path: one embed_sum
@@ -534,7 +606,8 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, text_hidden, z_style, max_new_tokens, prompt_tokens=None, start_token=0, text_mask=None,
                  ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, eos_id=None,
-                 pad_id=0, seed=0, check_every=32, prompt_lengths=None):
+                 pad_id=0, seed=0, check_every=32, prompt_lengths=None, repetition_penalty=None,
+                 repetition_window=64):
         """Autoregressive generation on the device: each new token is one
         replay of a hipGraph holding the decode step and the sampler
         (csrc/sample.hip), which writes the token buffer the next step embeds,
@@ -559,12 +632,37 @@ class DecodeEngine:
         reused: a decode_step sequence in flight on this engine does not
         survive a generate call (a following one, from step 0, does).
 
-        Returns tokens (B, n) int64, n <= max_new_tokens, and lengths (B,)."""
+        Per-request sampling: temperature, top_k, top_p, seed and
+        max_new_tokens each take a scalar or one value per row ((B,) list or
+        tensor), and repetition_penalty (scalar or (B,); None: off) divides
+        the positive and multiplies the other logits of every token among the
+        row's last `repetition_window` (0..256) GENERATED tokens -- the
+        history buffer; prompt tokens are not penalised.  With all of the
+        former scalar and no penalty the call runs exactly as described above
+        (the scalar sampler, its graph key, its tokens).  Otherwise the
+        per-row sampler (ops.sample_tokens_rows) draws: its controls are (B,)
+        device buffers filled per call, so the graph is keyed on ("rows",
+        eos_id, pad_id, repetition_window) alone and no per-row value captures
+        again.  Row b's random stream is a function of (seed_b, tokens row b
+        has drawn so far, v): the same request draws the same tokens in any
+        row of any batch.  A scalar seed becomes ops.row_seeds(seed, B).  A
+        row stops at its own max_new_tokens (pad_id afterwards); the loop runs
+        to the largest, and the early-stop poll also runs when the caps differ.
+
+        Returns tokens (B, n) int64, n <= max(max_new_tokens), and lengths (B,)."""
         m = self.m
         V = m.head.weight.shape[0]
         B = text_hidden.shape[0]
         dev = text_hidden.device
-        n_new = int(max_new_tokens)
+        per_row = (repetition_penalty is not None
+                   or not all(_is_scalar(v) for v in (temperature, top_k, top_p, seed, max_new_tokens)))
+        ctl = None
+        if per_row:
+            ctl = self._row_controls(B, temperature, top_k, top_p, seed, max_new_tokens, repetition_penalty,
+                                     repetition_window)
+            n_new = int(ctl["max_length"].max())
+        else:
+            n_new = int(max_new_tokens)
         if n_new < 1 or int(check_every) < 1:
             raise ValueError("generate: max_new_tokens and check_every must be >= 1")
         if prompt_tokens is not None and (prompt_tokens.dim() != 2 or prompt_tokens.shape[0] != B
@@ -594,10 +692,11 @@ class DecodeEngine:
                              f"({m.pos_embed.num_embeddings}) (index out of range in self)")
         if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
             raise ValueError(f"generate: pad_id / eos_id outside the vocabulary of {V}")
-        if not 0 < top_p <= 1:
-            raise ValueError("generate: top_p must be in (0, 1]")
-        if temperature < 0 or top_k < 0:
-            raise ValueError("generate: temperature and top_k must be >= 0")
+        if not per_row:
+            if not 0 < top_p <= 1:
+                raise ValueError("generate: top_p must be in (0, 1]")
+            if temperature < 0 or top_k < 0:
+                raise ValueError("generate: temperature and top_k must be >= 0")
         if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (B, V)):
             raise ValueError("generate: logit_bias must be (V,) or (B, V)")
         n_tok = m.token_embed.num_embeddings
@@ -614,11 +713,16 @@ class DecodeEngine:
         eos = None if eos_id is None else int(eos_id)
 
         def draw(logits):
-            ops.sample_tokens(logits, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
-                              logit_bias=g["bias"], seed=g["seed"], step=g["step"], advance=True, out=self.tok_buf,
-                              history=g["hist"], eos_id=eos, pad_id=int(pad_id), finished=g["finished"],
-                              length=g["length"], unfinished=g["unfinished"],
-                              pos=self.pos32 if self.fused else None)
+            common = dict(logit_bias=g["bias"], step=g["step"], advance=True, out=self.tok_buf, history=g["hist"],
+                          eos_id=eos, pad_id=int(pad_id), finished=g["finished"], length=g["length"],
+                          unfinished=g["unfinished"], pos=self.pos32 if self.fused else None)
+            if per_row:
+                ops.sample_tokens_rows(logits, temperature=g["temperature"], top_k=g["top_k"], top_p=g["top_p"],
+                                       seed=g["row_seed"], draw=g["draw"], penalty=g["penalty"],
+                                       window=ctl["window"], max_length=g["max_length"], **common)
+            else:
+                ops.sample_tokens(logits, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                                  seed=g["seed"], **common)
             if not self.fused:
                 self.pos_buf.add_(1)
 
@@ -626,7 +730,7 @@ class DecodeEngine:
             draw(stepfn(self.tok_buf, self.pos_buf, self.states)[:, 0])
 
         def rewind():
-            for t in (self.tok_buf, self.pos_buf, self.pos32, g["step"], g["finished"], g["length"]):
+            for t in (self.tok_buf, self.pos_buf, self.pos32, g["step"], g["finished"], g["length"], g["draw"]):
                 t.zero_()
             for cs, ss in self.states:
                 cs.zero_()
@@ -634,7 +738,8 @@ class DecodeEngine:
 
         run = body
         if self.use_graph:
-            key = (float(temperature), int(top_k), float(top_p), eos, int(pad_id))
+            key = (("rows", eos, int(pad_id), ctl["window"]) if per_row
+                   else (float(temperature), int(top_k), float(top_p), eos, int(pad_id)))
             gr = self.gen_graphs.get(key)
             if gr is None:
                 g["bias"].zero_()
@@ -653,8 +758,14 @@ class DecodeEngine:
             run = gr.replay
         # this call's state
         rewind()
-        g["seed"].fill_((int(seed) + (1 << 63)) % (1 << 64) - (1 << 63))
         g["unfinished"].fill_(B)
+        poll = eos is not None
+        if not per_row:
+            g["seed"].fill_((int(seed) + (1 << 63)) % (1 << 64) - (1 << 63))
+        else:
+            for name in ("temperature", "top_k", "top_p", "row_seed", "penalty", "max_length"):
+                g[name].copy_(ctl[name])
+            poll = poll or int(ctl["max_length"].min()) < n_new
         if logit_bias is None:
             g["bias"].zero_()
         else:
@@ -679,7 +790,7 @@ class DecodeEngine:
         while issued < n_new:
             run()
             issued += 1
-            if eos is not None and issued % int(check_every) == 0 and issued < n_new:
+            if poll and issued % int(check_every) == 0 and issued < n_new:
                 g["host"][polls:polls + 1].copy_(g["unfinished"], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -695,6 +806,6 @@ class DecodeEngine:
         self.check_errors()
         lengths = g["length"].clone()
         n = issued
-        if eos is not None and int(g["unfinished"].item()) == 0:
+        if poll and int(g["unfinished"].item()) == 0:
             n = int(lengths.max())                  # trimmed at the step where every row had finished
         return g["hist"][:, :n].clone(), lengths

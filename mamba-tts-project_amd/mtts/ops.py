@@ -856,6 +856,55 @@ def _dev_scalar(v, dtype, dev, name):
     return torch.full((1,), int(v), dtype=dtype, device=dev)
 
 
+def _sample_io(a, fn, logits, logit_bias, step, advance, out, history, step0, eos_id, pad_id, finished, length,
+               unfinished, pos):
+    """What both sampler structs share: checks the tensors and fills logits,
+    bias, counters, outputs and the end-of-sequence bookkeeping into `a`.
+    Returns `out` and the step tensor (to be kept alive across the call)."""
+    _check_cuda(logits, logit_bias, out, history, finished, length, unfinished, pos)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"{fn}: logits must be (rows, V) with unit column stride")
+    rows, V = logits.shape
+    dev = logits.device
+    if not 0 <= pad_id < V or (eos_id is not None and not 0 <= eos_id < V):
+        raise ValueError(f"{fn}: pad_id / eos_id outside the vocabulary")
+    a.rows, a.vocab, a.dtype = rows, V, L.dtype_code(logits)
+    a.ld, a.logits = logits.stride(0) if rows > 1 else max(logits.stride(0), V), logits.data_ptr()
+    if logit_bias is not None:
+        if (logit_bias.dtype != torch.float32 or logit_bias.stride(-1) != 1
+                or tuple(logit_bias.shape) not in ((V,), (rows, V))):
+            raise ValueError(f"{fn}: logit_bias must be fp32 (V,) or (rows, V) with unit column stride")
+        a.bias = logit_bias.data_ptr()
+        a.bias_ld = logit_bias.stride(0) if logit_bias.dim() == 2 and rows > 1 else 0
+    step_t = _dev_scalar(step, torch.int32, dev, "step")
+    a.step, a.advance, a.step0 = step_t.data_ptr(), int(bool(advance)), int(step0)
+    if pos is not None:
+        if pos.dtype != torch.int32 or not pos.is_contiguous() or (pos.numel() != 1 and tuple(pos.shape) != (rows,)):
+            raise ValueError(f"{fn}: pos must be a one-element or a contiguous (rows,) int32 tensor")
+        a.pos, a.pos_rows = pos.data_ptr(), rows if pos.numel() > 1 else 0
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=dev)
+    if out.dtype != torch.int64 or out.numel() != rows:
+        raise ValueError(f"{fn}: out must hold one int64 per row")
+    flat = out.reshape(-1) if out.dim() != 1 else out
+    if flat.data_ptr() != out.data_ptr():
+        raise ValueError(f"{fn}: out must be viewable as one strided vector")
+    a.tokens, a.tok_stride = out.data_ptr(), flat.stride(0) if rows > 1 else 1
+    if history is not None:
+        if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or history.stride(1) != 1:
+            raise ValueError(f"{fn}: history must be (rows, n) int64 with unit column stride")
+        a.history, a.hist_ld, a.hist_cols = history.data_ptr(), max(history.stride(0), history.shape[1]), history.shape[1]
+    a.eos_id, a.pad_id = -1 if eos_id is None else int(eos_id), int(pad_id)
+    for t, dt, n, name in ((finished, torch.int32, rows, "finished"), (length, torch.int64, rows, "length"),
+                           (unfinished, torch.int32, 1, "unfinished")):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous {dt} tensor of {n} element(s)")
+    if unfinished is not None and finished is None:
+        raise ValueError(f"{fn}: unfinished needs finished")
+    a.finished, a.length, a.unfinished = L.ptr(finished), L.ptr(length), L.ptr(unfinished)
+    return out, step_t
+
+
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, seed, step, advance=False,
                   out=None, history=None, step0=0, eos_id=None, pad_id=0, finished=None, length=None,
                   unfinished=None, pos=None):
@@ -878,51 +927,83 @@ def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=Non
     pad_id and keeps its length, a row becomes finished on emitting eos_id,
     and `unfinished` is rewritten with the number of rows still running.
     Returns the tokens."""
-    _check_cuda(logits, logit_bias, out, history, finished, length, unfinished, pos)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1 or logits.shape[1] < 1:
-        raise ValueError("sample_tokens: logits must be (rows, V) with unit column stride")
-    rows, V = logits.shape
-    dev = logits.device
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError("sample_tokens: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
-    if not 0 <= pad_id < V or (eos_id is not None and not 0 <= eos_id < V):
-        raise ValueError("sample_tokens: pad_id / eos_id outside the vocabulary")
     a = L.SampleArgs()
-    a.rows, a.vocab, a.dtype, a.top_k = rows, V, L.dtype_code(logits), int(top_k)
-    a.ld, a.logits = logits.stride(0) if rows > 1 else max(logits.stride(0), V), logits.data_ptr()
-    if logit_bias is not None:
-        if (logit_bias.dtype != torch.float32 or logit_bias.stride(-1) != 1
-                or tuple(logit_bias.shape) not in ((V,), (rows, V))):
-            raise ValueError("sample_tokens: logit_bias must be fp32 (V,) or (rows, V) with unit column stride")
-        a.bias = logit_bias.data_ptr()
-        a.bias_ld = logit_bias.stride(0) if logit_bias.dim() == 2 and rows > 1 else 0
-    a.temperature, a.top_p = float(temperature), float(top_p)
-    seed_t = _dev_scalar(seed, torch.int64, dev, "seed")
-    step_t = _dev_scalar(step, torch.int32, dev, "step")
-    a.seed, a.step, a.advance, a.step0 = seed_t.data_ptr(), step_t.data_ptr(), int(bool(advance)), int(step0)
-    if pos is not None:
-        if pos.dtype != torch.int32 or not pos.is_contiguous() or (pos.numel() != 1 and tuple(pos.shape) != (rows,)):
-            raise ValueError("sample_tokens: pos must be a one-element or a contiguous (rows,) int32 tensor")
-        a.pos, a.pos_rows = pos.data_ptr(), rows if pos.numel() > 1 else 0
-    if out is None:
-        out = torch.empty(rows, dtype=torch.int64, device=dev)
-    if out.dtype != torch.int64 or out.numel() != rows:
-        raise ValueError("sample_tokens: out must hold one int64 per row")
-    flat = out.reshape(-1) if out.dim() != 1 else out
-    if flat.data_ptr() != out.data_ptr():
-        raise ValueError("sample_tokens: out must be viewable as one strided vector")
-    a.tokens, a.tok_stride = out.data_ptr(), flat.stride(0) if rows > 1 else 1
-    if history is not None:
-        if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or history.stride(1) != 1:
-            raise ValueError("sample_tokens: history must be (rows, n) int64 with unit column stride")
-        a.history, a.hist_ld, a.hist_cols = history.data_ptr(), max(history.stride(0), history.shape[1]), history.shape[1]
-    a.eos_id, a.pad_id = -1 if eos_id is None else int(eos_id), int(pad_id)
-    for t, dt, n, name in ((finished, torch.int32, rows, "finished"), (length, torch.int64, rows, "length"),
-                           (unfinished, torch.int32, 1, "unfinished")):
-        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
-            raise ValueError(f"sample_tokens: {name} must be a contiguous {dt} tensor of {n} element(s)")
-    if unfinished is not None and finished is None:
-        raise ValueError("sample_tokens: unfinished needs finished")
-    a.finished, a.length, a.unfinished = L.ptr(finished), L.ptr(length), L.ptr(unfinished)
+    out, _step_t = _sample_io(a, "sample_tokens", logits, logit_bias, step, advance, out, history, step0, eos_id,
+                              pad_id, finished, length, unfinished, pos)
+    a.top_k, a.temperature, a.top_p = int(top_k), float(temperature), float(top_p)
+    seed_t = _dev_scalar(seed, torch.int64, logits.device, "seed")
+    a.seed = seed_t.data_ptr()
     L.call("mtts_sample_tokens", a)
+    return out
+
+
+GOLDEN64 = 0x9E3779B97F4A7C15
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """splitmix64's finalizer on a Python int (mod 2^64), as csrc/sample.hip."""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def row_seeds(seed, rows):
+    """The documented expansion of one integer seed into per-row seeds for
+    sample_tokens_rows: seed_r = int64(mix64(seed + (r + 1) * 0x9E3779B97F4A7C15))
+    (64-bit wrapping).  Host integer arithmetic; returns a list of `rows`
+    Python ints in the int64 range."""
+    out = []
+    for r in range(int(rows)):
+        z = _mix64((int(seed) + (r + 1) * GOLDEN64) & _M64)
+        out.append(z - (1 << 64) if z >> 63 else z)
+    return out
+
+
+def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
+                       logit_bias=None, step, advance=False, out=None, history=None, step0=0, eos_id=None, pad_id=0,
+                       finished=None, length=None, unfinished=None, pos=None):
+    """sample_tokens with per-row controls read from device memory at run
+    time (include/mtts.h, MttsSampleRowsArgs, has the exact definition): rows
+    of one launch, and replays of one captured launch, may differ in all of
+    them.  Contiguous (rows,) device tensors:
+    temperature fp32 (!(T > 0): greedy), top_k int32 (<= 0 or >= V: off),
+    top_p fp32 (outside (0, 1): off), seed int64, draw int32 (tokens this row
+    has drawn so far; the kernel adds one for every row that is not finished),
+    penalty fp32, optional (repetition penalty; 1: off), max_length int64,
+    optional (needs finished and length: a row finishes once its length
+    reaches it).
+    The random stream of a row is a function of (seed[r], draw[r], v) only, so
+    a request draws the same tokens in any row of any batch.
+    window (int, 0..256): the penalty applies once to each distinct id among
+    the row's last min(window, draw[r], step - step0) history columns (ids
+    outside [0, V) are skipped); it needs `history`.
+    Everything else is as in sample_tokens.  No device value is read here."""
+    fn = "sample_tokens_rows"
+    a = L.SampleRowsArgs()
+    out, _step_t = _sample_io(a, fn, logits, logit_bias, step, advance, out, history, step0, eos_id, pad_id,
+                              finished, length, unfinished, pos)
+    rows, dev = logits.shape[0], logits.device
+    per_row = (("temperature", temperature, torch.float32, True), ("top_k", top_k, torch.int32, True),
+               ("top_p", top_p, torch.float32, True), ("seed", seed, torch.int64, True),
+               ("draw", draw, torch.int32, True), ("penalty", penalty, torch.float32, False),
+               ("max_length", max_length, torch.int64, False))
+    for name, t, dt, required in per_row:
+        if t is None and not required:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (rows,)
+                or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous ({rows},) {dt} tensor on {dev}")
+        setattr(a, name, t.data_ptr())
+    window = int(window)
+    if not 0 <= window <= 256:
+        raise ValueError(f"{fn}: window must lie in [0, 256]")
+    if window > 0 and history is None:
+        raise ValueError(f"{fn}: window > 0 needs history")
+    if max_length is not None and (finished is None or length is None):
+        raise ValueError(f"{fn}: max_length needs finished and length")
+    a.window = window
+    L.call("mtts_sample_tokens_rows", a)
     return out

@@ -9,7 +9,11 @@ repeats each; vocabulary 10 and 1024, greedy and top_k=50 / top_p=0.9.
 prefill with prompt_lengths against the rectangular prefill and against
 stepping the prompt columns through decode_step, and the per-token time of
 the ragged continuation against the rectangular one (the same graph).
-python tools/generate_ab.py [--steps 512] [--ragged] [--out FILE]"""
+--rows runs the per-row sampling leg instead (vocabulary 10 and 1024, top_k=50
+/ top_p=0.9): (a) the scalar path, (b) the per-row path with the same
+settings in every row and no penalty, (c) the per-row path with
+repetition_penalty 1.3 over a window of 64.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -96,18 +100,49 @@ def ragged_leg(n, dev, lines):
         print(ln, flush=True)
 
 
+def rows_leg(n, dev, lines):
+    import mamba_decoder
+    lines.append(f"per-row sampling, C4 (12L d=1024 B=32 bf16), {n} steps, top_k=50 top_p=0.9, us per token "
+                 "(three interleaved repeats, min first; spread = max - min)")
+    for vocab in (10, 1024):
+        c = dict(bench.C2)
+        c["B"] = 32
+        torch.manual_seed(0)
+        m = mamba_decoder.MambaTTSDecoder(vocab, d_model=c["d_model"], n_layers=c["n_layers"], n_heads=c["n_heads"],
+                                          d_ff=c["d_ff"], d_style=c["d_style"]).to(dev).eval()
+        m.compute_dtype = torch.bfloat16
+        _, text, z, mask = bench.make_batch(c, dev, 7)
+        kw = dict(top_k=50, top_p=0.9, text_mask=mask, seed=1)
+        cases = (("(a) scalar path", dict(temperature=1.0)),
+                 ("(b) per-row path, no penalty", dict(temperature=[1.0] * 32)),
+                 ("(c) per-row path, penalty 1.3 window 64",
+                  dict(temperature=[1.0] * 32, repetition_penalty=1.3, repetition_window=64)))
+        for _, extra in cases:
+            m.generate(text, z, n, **kw, **extra)      # capture / warm up
+        res = [[] for _ in cases]
+        for _ in range(3):
+            for r, (_, extra) in zip(res, cases):
+                r.append(timed(lambda: m.generate(text, z, n, **kw, **extra)) * 1e3 / n)
+        for (name, _), r in zip(cases, res):
+            lines.append(f"vocab {vocab:5d} {name:42s} {min(r):7.1f} (" + " ".join(f"{v:.1f}" for v in r)
+                         + f")  spread {max(r) - min(r):.1f}  vs (a) {min(r) - min(res[0]):+.1f}")
+            print(lines[-1], flush=True)
+        lines.append(f"vocab {vocab:5d} graphs captured {len(m._engine.gen_graphs)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--ragged", action="store_true", help="run the ragged-prompt leg instead")
+    ap.add_argument("--rows", action="store_true", help="run the per-row sampling leg instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged:
+    if args.ragged or args.rows:
         lines = []
-        ragged_leg(n, dev, lines)
+        (ragged_leg if args.ragged else rows_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
