@@ -40,7 +40,9 @@ extern "C" {
  * that needs the additions checks that mtts_embed_sum_at resolves.  The
  * per-row token sampler (MttsSampleRowsArgs, mtts_sample_tokens_rows) is
  * additive in the same way: MttsSampleArgs and mtts_sample_tokens are
- * untouched, and a binding that needs it checks that the symbol resolves. */
+ * untouched, and a binding that needs it checks that the symbol resolves.
+ * So is its slot form, mtts_sample_tokens_slots: one more symbol on the same
+ * struct. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -956,6 +958,35 @@ typedef struct {
 } MttsSampleRowsArgs;
 
 int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Slot form of the per-row sampler (an addition within ABI 15; a binding that
+ * needs it checks that the symbol resolves).  For a decode session whose rows
+ * ("slots") hold requests admitted at different times.  It takes the struct
+ * above and is the per-row form -- the same stream, filters, penalty
+ * arithmetic, max_length and eos_id -- except for:
+ *   history column: row r's column is its own col_r = draw[r] at entry, not
+ *                   *step - step0; `step` and `step0` do not enter it.  The
+ *                   token goes to history[r, col_r] when 0 <= col_r <
+ *                   hist_cols, and the penalty window is the last
+ *                   n = min(window, draw[r]) columns before col_r of the
+ *                   row's own history (nothing for draw[r] <= 0).
+ *   finished rows:  a row with finished[r] != 0 at entry has pad_id written
+ *                   to tokens[r] and nothing else: its history, draw[r] and
+ *                   length[r] stay, so a finished request's tokens are
+ *                   intact until the host has taken them.
+ *   step:           may be NULL even with `advance`; when given and `advance`
+ *                   is set it is still incremented, but nothing reads it.
+ *   pos:            with `advance` and `pos`, pos_rows must be 0 or rows.
+ *                   pos_rows == rows: the one-workgroup launch behind the
+ *                   sampler adds one to pos[r] only for rows with
+ *                   finished[r] == 0 AFTER the draw (finished == NULL: every
+ *                   row), so a row that ends in this launch, or idles past
+ *                   its end, keeps its position.  pos_rows == 0: the single
+ *                   counter *pos moves as in MttsSampleArgs.
+ * *unfinished is rewritten as before.
+ * ------------------------------------------------------------------------ */
+int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream);
 
 #ifdef __cplusplus
 }

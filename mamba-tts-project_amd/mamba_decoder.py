@@ -400,3 +400,29 @@ class MambaTTSDecoder(nn.Module):
                                      logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
                                      check_every=check_every, repetition_penalty=repetition_penalty,
                                      repetition_window=repetition_window)
+
+    def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64):
+        """A decode session for continuous batching (mtts/session.py
+        DecodeSession): `slots` rows over static per-slot buffers, conditioning
+        of up to `max_keys` keys per request, one captured graph of step +
+        slot sampler.  admit(slot, ...) puts a request into an idle slot,
+        run(n) draws n tokens for every live slot, poll() lists the finished
+        slots and take(slot) returns a finished request's tokens and frees
+        the slot.  The session owns its buffers and its graph: generate() and
+        decode_step before, during and after it behave as without one."""
+        if not self.decode_mode:
+            raise RuntimeError("open_session runs on the decode engine: set decode_mode to 'graph' or 'eager'")
+        from mtts.session import DecodeSession
+        return DecodeSession(self, slots, max_keys, eos_id=eos_id, pad_id=pad_id,
+                             repetition_window=repetition_window, use_graph=self.decode_mode == "graph")
+
+    def generate_requests(self, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
+                          repetition_window=64):
+        """A queue of requests through one session of `slots` rows, refilled
+        as rows finish (mtts/session.py generate_requests, by the policy of
+        mtts.session.plan_slots).  `requests`: dicts of admit's arguments.
+        Returns (token tensors in request order, the slot of every request,
+        the number of replays made)."""
+        from mtts.session import generate_requests
+        return generate_requests(self, requests, slots=slots, max_keys=max_keys, check_every=check_every,
+                                 eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window)

@@ -224,6 +224,7 @@ _SIGS = {
     "mtts_dropout": ([C.POINTER(DropoutArgs), vp], i32),
     "mtts_sample_tokens": ([C.POINTER(SampleArgs), vp], i32),
     "mtts_sample_tokens_rows": ([C.POINTER(SampleRowsArgs), vp], i32),
+    "mtts_sample_tokens_slots": ([C.POINTER(SampleRowsArgs), vp], i32),
 }
 
 _lib = None
@@ -241,6 +242,7 @@ def lib():
         # the same version: the added symbols tell them apart
         for sym, what in (("mtts_embed_sum_at", "ragged prompts"),
                           ("mtts_sample_tokens_rows", "per-row sampling"),
+                          ("mtts_sample_tokens_slots", "decode sessions"),
                           ("mtts_gemm_grouped_rounds", "round-filling weight gradients")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "

@@ -38,6 +38,13 @@
 // LDS-staged row is penalised as it is staged and a longer row on every
 // re-read; every pass downstream sees the penalised value.  The scalar form
 // instantiates none of this.
+//
+// The slot form (mtts_sample_tokens_slots) is the per-row form for a decode
+// session whose rows are requests admitted at different times: the history
+// column is the row's own draw count instead of the shared step, a finished
+// row keeps its history until the host has taken it, and the launch behind
+// the sampler advances the positions of the unfinished rows only.  One more
+// instantiation (kSlots); the other two compile none of it.
 #include "common.h"
 
 #include <math.h>
@@ -126,10 +133,17 @@ __device__ __forceinline__ float gumbel(uint32_t n) {
 struct SampleParams {
   MttsSampleArgs a;
   static constexpr bool kRows = false;
+  static constexpr bool kSlots = false;
 };
 struct SampleRowsParams {   // the per-row form: controls read from device arrays (mtts_sample_tokens_rows)
   MttsSampleRowsArgs a;
   static constexpr bool kRows = true;
+  static constexpr bool kSlots = false;
+};
+struct SampleSlotsParams {  // the slot form: the per-row form on the row's own history column (mtts_sample_tokens_slots)
+  MttsSampleRowsArgs a;
+  static constexpr bool kRows = true;
+  static constexpr bool kSlots = true;
 };
 
 // The per-row form's penalty window as a set: open addressing over kWinSlots
@@ -163,6 +177,7 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   constexpr int kThreads = NW * 64;
   constexpr int kCache = NW == 1 ? kSampleWaveV : kSampleCache;
   constexpr bool kRows = P::kRows;
+  constexpr bool kSlots = P::kSlots;
   const auto& p = prm.a;
   __shared__ float xs[kCache];
   __shared__ float es[kCache];
@@ -170,8 +185,13 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   __shared__ int wtab[kRows ? kWinSlots : 1];
   int phase = 0;
   const int row = blockIdx.x, tid = threadIdx.x, V = p.vocab;
-  const int step = p.step ? *p.step : 0;
-  const int col = step - p.step0;
+  int step = 0, col;
+  if constexpr (kSlots) {
+    col = p.draw[row];   // the row's own column: neither *step nor step0 enters
+  } else {
+    step = p.step ? *p.step : 0;
+    col = step - p.step0;
+  }
   int64_t* const hist = (p.history && col >= 0 && col < p.hist_cols) ? p.history + (int64_t)row * p.hist_ld + col
                                                                      : nullptr;
   int64_t* const tok_out = p.tokens + (int64_t)row * p.tok_stride;
@@ -197,7 +217,9 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   if (p.finished && p.finished[row] != 0) {   // past its end of sequence: pad, length frozen
     if (tid == 0) {
       *tok_out = p.pad_id;
-      if (hist) *hist = p.pad_id;
+      if constexpr (!kSlots) {   // a slot keeps its finished request's tokens until the host takes them
+        if (hist) *hist = p.pad_id;
+      }
     }
     return;
   }
@@ -351,6 +373,32 @@ __global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* ste
     for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads) pos[r] += 1;
 }
 
+// The slot form's launch behind the sampler: as above, but a per-row position
+// moves only when its row is unfinished after the draw, so a row idling past
+// its end stays inside pos_embed however long its slot waits for a request.
+__global__ __launch_bounds__(kSampleThreads) void sample_advance_slots_kernel(int* step, int* pos,
+                                                                              const int* finished, int rows,
+                                                                              int* unfinished, int advance,
+                                                                              int pos_rows) {
+  __shared__ uint64_t slots[2][4];
+  int phase = 0;
+  uint32_t done = 0;
+  if (unfinished) {
+    for (int r = threadIdx.x; r < rows; r += kSampleThreads) done += finished[r] != 0 ? 1u : 0u;
+    done = block_red<4>(done, OpSum(), slots, phase);
+  }
+  if (threadIdx.x == 0) {
+    if (unfinished) *unfinished = rows - (int)done;
+    if (advance) {
+      if (step) *step += 1;
+      if (pos && pos_rows <= 0) *pos += 1;
+    }
+  }
+  if (advance && pos && pos_rows > 0)
+    for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads)
+      if (!finished || finished[r] == 0) pos[r] += 1;
+}
+
 }  // namespace
 }  // namespace mtts
 
@@ -433,6 +481,49 @@ extern "C" int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
                        a->rows, a->unfinished, a->advance, a->pos_rows);
     MTTS_LAUNCH_CHECK("sample_tokens_rows (advance)");
+  }
+  return MTTS_OK;
+}
+
+extern "C" int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream) {
+  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens_slots: null pointer");
+  MTTS_CHECK(a->temperature && a->top_k && a->top_p && a->seed && a->draw,
+             "sample_tokens_slots: temperature, top_k, top_p, seed and draw are required");
+  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens_slots: dtype must be f32 or bf16");
+  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24),
+             "sample_tokens_slots: rows=%d vocab=%d out of range", a->rows, a->vocab);
+  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
+             "sample_tokens_slots: row stride below vocab");
+  MTTS_CHECK(a->window >= 0 && a->window <= MTTS_SAMPLE_WINDOW_MAX, "sample_tokens_slots: window=%d outside [0, %d]",
+             a->window, MTTS_SAMPLE_WINDOW_MAX);
+  MTTS_CHECK(a->window == 0 || a->history, "sample_tokens_slots: window=%d needs history", a->window);
+  MTTS_CHECK(!a->max_length || (a->finished && a->length), "sample_tokens_slots: max_length needs finished and length");
+  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
+             "sample_tokens_slots: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
+  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols),
+             "sample_tokens_slots: bad history shape");
+  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens_slots: unfinished needs finished");
+  MTTS_CHECK(!(a->advance && a->pos) || a->pos_rows == 0 || a->pos_rows == a->rows,
+             "sample_tokens_slots: pos_rows=%d must be 0 or rows=%d", a->pos_rows, a->rows);
+  hipStream_t st = (hipStream_t)stream;
+  SampleSlotsParams prm;
+  prm.a = *a;
+  const bool f32 = a->dtype == MTTS_F32;
+  if (a->vocab <= kSampleWaveV) {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleSlotsParams>), dim3(a->rows), dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleSlotsParams>), dim3(a->rows), dim3(64), 0, st, prm);
+  } else {
+    if (f32)
+      hipLaunchKernelGGL((sample_kernel<float, 4, SampleSlotsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    else
+      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleSlotsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st,
+                         prm);
+  }
+  MTTS_LAUNCH_CHECK("sample_tokens_slots");
+  if (a->advance || a->unfinished) {
+    hipLaunchKernelGGL(sample_advance_slots_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos,
+                       a->finished, a->rows, a->unfinished, a->advance, a->pos_rows);
+    MTTS_LAUNCH_CHECK("sample_tokens_slots (advance)");
   }
   return MTTS_OK;
 }

@@ -30,6 +30,9 @@ Engine path (inference only: torch.no_grad, HIP tensors):
     Per-request sampling (per-row temperature / top-k / top-p / seed / length
     cap, repetition penalty) goes through the per-row sampler, whose controls
     are (B,) device buffers too: one graph serves every mix of settings.
+  * continuous batching (mtts/session.py DecodeSession): the same step
+    functions over static per-slot buffers of a private engine, finished
+    rows refilled in place under one captured graph.
 Numerics are those of the eager module path (tests/test_gpu_modules.py).
 Call `reset()` after modifying weights in place between decode steps.
 """

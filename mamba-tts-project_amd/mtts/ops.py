@@ -876,8 +876,8 @@ def _sample_io(a, fn, logits, logit_bias, step, advance, out, history, step0, eo
             raise ValueError(f"{fn}: logit_bias must be fp32 (V,) or (rows, V) with unit column stride")
         a.bias = logit_bias.data_ptr()
         a.bias_ld = logit_bias.stride(0) if logit_bias.dim() == 2 and rows > 1 else 0
-    step_t = _dev_scalar(step, torch.int32, dev, "step")
-    a.step, a.advance, a.step0 = step_t.data_ptr(), int(bool(advance)), int(step0)
+    step_t = None if step is None else _dev_scalar(step, torch.int32, dev, "step")   # None: the slot form only
+    a.step, a.advance, a.step0 = L.ptr(step_t), int(bool(advance)), int(step0)
     if pos is not None:
         if pos.dtype != torch.int32 or not pos.is_contiguous() or (pos.numel() != 1 and tuple(pos.shape) != (rows,)):
             raise ValueError(f"{fn}: pos must be a one-element or a contiguous (rows,) int32 tensor")
@@ -1006,4 +1006,49 @@ def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty
         raise ValueError(f"{fn}: max_length needs finished and length")
     a.window = window
     L.call("mtts_sample_tokens_rows", a)
+    return out
+
+
+def sample_tokens_slots(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
+                        logit_bias=None, step=None, advance=False, out=None, history=None, eos_id=None, pad_id=0,
+                        finished=None, length=None, unfinished=None, pos=None):
+    """sample_tokens_rows for the rows ("slots") of a decode session, whose
+    requests were admitted at different times (include/mtts.h,
+    mtts_sample_tokens_slots, has the exact definition).  It differs in this:
+    row r's history column is its own draw[r] at entry -- the token goes to
+    history[r, draw[r]] and the penalty covers the last min(window, draw[r])
+    columns before it -- so there is no step0 and `step` is optional (None, or
+    a one-element int32 device tensor that advance=True still increments);
+    a row finished at entry gets pad_id in `out` and keeps its history, draw
+    and length; and advance=True with per-row `pos` moves only the rows that
+    are unfinished after the draw.  No device value is read here."""
+    fn = "sample_tokens_slots"
+    a = L.SampleRowsArgs()
+    if step is not None and not isinstance(step, torch.Tensor):
+        raise ValueError(f"{fn}: step must be None or a one-element int32 device tensor")
+    out, _step_t = _sample_io(a, fn, logits, logit_bias, step, advance, out, history, 0, eos_id, pad_id, finished,
+                              length, unfinished, pos)
+    rows, dev = logits.shape[0], logits.device
+    if pos is not None and pos.numel() == rows:
+        a.pos_rows = rows                       # one row is a per-row position too: gated by its finished flag
+    per_row = (("temperature", temperature, torch.float32, True), ("top_k", top_k, torch.int32, True),
+               ("top_p", top_p, torch.float32, True), ("seed", seed, torch.int64, True),
+               ("draw", draw, torch.int32, True), ("penalty", penalty, torch.float32, False),
+               ("max_length", max_length, torch.int64, False))
+    for name, t, dt, required in per_row:
+        if t is None and not required:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (rows,)
+                or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous ({rows},) {dt} tensor on {dev}")
+        setattr(a, name, t.data_ptr())
+    window = int(window)
+    if not 0 <= window <= 256:
+        raise ValueError(f"{fn}: window must lie in [0, 256]")
+    if window > 0 and history is None:
+        raise ValueError(f"{fn}: window > 0 needs history")
+    if max_length is not None and (finished is None or length is None):
+        raise ValueError(f"{fn}: max_length needs finished and length")
+    a.window = window
+    L.call("mtts_sample_tokens_slots", a)
     return out

@@ -1,0 +1,429 @@
+"""Continuous batching for MambaTTSDecoder: a decode session whose rows
+("slots") hold requests admitted at different times.
+
+generate() is a batch call: every row starts together and a row that has
+reached its cap idles until the longest one is done.  A Mamba decoder keeps
+O(1) state per row, so a finished row can be handed to the next request at
+once.  DecodeSession keeps everything a request owns as one row of static
+device buffers -- its conditioning K/V over `max_keys` keys, key-padding mask,
+FiLM rows, conv / SSM states, token, position, sampler controls, history --
+and replays ONE captured graph of the engine's decode step plus the slot form
+of the sampler (ops.sample_tokens_slots: the history column is the row's own
+draw count, finished rows keep their tokens and their position).  Admitting a
+request rewrites its slot's rows in place, stream-ordered; no admission,
+control value or seed captures again.  A request's random stream is a function
+of (seed, tokens drawn so far, v) and every kernel of the step is row-wise, so
+its tokens do not depend on its slot, its neighbours or the schedule.
+
+plan_slots() is the refill policy as a pure host function;
+generate_requests() runs a queue of requests through a session by it.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+
+from . import ops
+from .decode import DecodeEngine, _is_scalar
+from .linear import cast_weight
+
+
+def plan_slots(caps, slots, check_every, prefilled=None):
+    """The refill policy of generate_requests for length caps `caps` (one per
+    request, in order) on `slots` rows: admit in order into the lowest free
+    slot; replay min(check_every, the largest number of tokens a live row has
+    left) times; take what has finished; refill.  prefilled[i] true: request
+    i draws its first token at admission (a prompt of more than one token),
+    so it needs one replay less.  Returns (slot of every request, replays)."""
+    caps = [int(c) for c in caps]
+    slots, check_every = int(slots), int(check_every)
+    if slots < 1 or check_every < 1 or any(c < 1 for c in caps):
+        raise ValueError("plan_slots: slots, check_every and every cap must be >= 1")
+    pre = [False] * len(caps) if prefilled is None else [bool(p) for p in prefilled]
+    if len(pre) != len(caps):
+        raise ValueError("plan_slots: prefilled must hold one value per request")
+    left = [None] * slots                   # tokens the slot's request has still to draw (None: free)
+    where, nxt, replays = [], 0, 0
+    while nxt < len(caps) or any(v is not None for v in left):
+        for s in range(slots):
+            if left[s] is None and nxt < len(caps):
+                left[s] = caps[nxt] - (1 if pre[nxt] else 0)
+                where.append(s)
+                nxt += 1
+        n = min(check_every, max(v for v in left if v is not None))
+        replays += n
+        left = [None if v is None or v - n <= 0 else v - n for v in left]
+    return where, replays
+
+
+class DecodeSession:
+    """See the module docstring; made by MambaTTSDecoder.open_session."""
+
+    CAPTURES = 0        # graphs captured by every session of the process (tests count them)
+
+    @torch.no_grad()
+    def __init__(self, model, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, use_graph=True):
+        m = self.m = model
+        V = m.head.weight.shape[0]
+        slots, max_keys = int(slots), int(max_keys)
+        if slots < 1 or max_keys < 1:
+            raise ValueError("open_session: slots and max_keys must be >= 1")
+        if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
+            raise ValueError(f"open_session: pad_id / eos_id outside the vocabulary of {V}")
+        w = repetition_window
+        if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 256:
+            raise ValueError("open_session: repetition_window must be an integer in [0, 256]")
+        dev = m.token_embed.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("open_session runs on the HIP kernels only (no CPU path)")
+        self.slots, self.max_keys, self.V = slots, max_keys, V
+        self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), w
+        self.use_graph = bool(use_graph)
+        self.dev = dev
+        d = m.token_embed.weight.shape[1]
+        cd = self.cd = m._cd()
+        P = self.P = m.pos_embed.num_embeddings
+        # a private engine: the step functions and their predicates are the engine's, the buffers are ours
+        eng = self.eng = DecodeEngine(m, use_graph=False)
+        keep = torch.zeros(slots, max_keys, dtype=torch.bool, device=dev)
+        keep[:, 0] = True                                   # a fully masked row would give NaN
+        ds = m.layers[0].style_mlp[0].weight.shape[1]
+        ctx = eng._build_ctx(torch.zeros(slots, max_keys, d, device=dev, dtype=cd),
+                             torch.zeros(slots, ds, device=dev), keep, None, None, cd)
+        self.kpm = ctx["kpm"]                               # (slots, max_keys) bool, True = ignore: rewritten in place
+        for l, p in zip(m.layers, ctx["layers"]):
+            ca = l.cross_attn
+            p["Wkv"] = cast_weight(ca.in_proj_weight, cd)[d:]
+            p["bkv"] = cast_weight(ca.in_proj_bias, cd)[d:]
+            for name in ("k", "v", "gamma", "beta"):        # idle rows are zero
+                p[name].zero_()
+        eng.ctx = ctx
+        eng.fused = eng._fused_ok(cd, slots)
+        if eng.fused and eng.OPTIONS["packed"]:
+            eng._pack_ctx()
+        eng.xpk = eng.fused and eng._xpk_ok()               # also makes khm / vhm and the packed FiLM images
+        eng.fuse_q = eng.xpk and eng.OPTIONS["fuse_q"] and eng._fuse_q_ok(slots)
+        eng.states = [(torch.zeros(slots, l.mamba.d_inner, l.mamba.d_conv, device=dev),
+                       torch.zeros(slots, l.mamba.d_inner, l.mamba.d_state, device=dev)) for l in m.layers]
+        eng.tok_buf = torch.full((slots, 1), self.pad, dtype=torch.long, device=dev)
+        eng.pos_buf = torch.zeros(slots, dtype=torch.long, device=dev)
+        eng.pos32 = torch.zeros(slots, dtype=torch.int32, device=dev)
+        # the batch-1 prefill runs on an engine of its own states; the context's constants are shared
+        pre = self.pre = DecodeEngine(m, use_graph=False)
+        pre.ctx = ctx
+        pre.states = [(torch.zeros(1, *cs.shape[1:], device=dev), torch.zeros(1, *ss.shape[1:], device=dev))
+                      for cs, ss in eng.states]
+        # length (int64) and finished (int32) share one allocation: a poll is one copy
+        self._raw = torch.zeros(12 * slots, dtype=torch.uint8, device=dev)
+        self._raw_host = torch.zeros(12 * slots, dtype=torch.uint8, pin_memory=True)
+        self.length = self._raw[:8 * slots].view(torch.int64)
+        self.finished = self._raw[8 * slots:].view(torch.int32)
+        self.finished.fill_(1)
+        self.g = dict(
+            temperature=torch.zeros(slots, dtype=torch.float32, device=dev),
+            top_k=torch.zeros(slots, dtype=torch.int32, device=dev),
+            top_p=torch.ones(slots, dtype=torch.float32, device=dev),
+            row_seed=torch.zeros(slots, dtype=torch.int64, device=dev),
+            draw=torch.zeros(slots, dtype=torch.int32, device=dev),
+            penalty=torch.ones(slots, dtype=torch.float32, device=dev),
+            max_length=torch.full((slots,), P, dtype=torch.int64, device=dev),
+            hist=torch.zeros(slots, P, dtype=torch.int64, device=dev),
+            unfinished=torch.zeros(1, dtype=torch.int32, device=dev),
+            bias=torch.zeros(slots, V, dtype=torch.float32, device=dev))
+        self.logits = torch.zeros(slots, V, device=dev, dtype=cd)
+        self.state = ["idle"] * slots                       # idle -> live (admit) -> done (poll) -> idle (take)
+        self.lengths = [0] * slots
+        self.graph = None
+        self.captures = 0
+        self.replays = 0
+        if self.use_graph:
+            self._capture()
+
+    # -- the step ---------------------------------------------------------------
+    def _sample(self, logits, rows):
+        """The slot form of the sampler on `rows` (a slice) of the slot buffers."""
+        g, eng = self.g, self.eng
+        ops.sample_tokens_slots(
+            logits, temperature=g["temperature"][rows], top_k=g["top_k"][rows], top_p=g["top_p"][rows],
+            seed=g["row_seed"][rows], draw=g["draw"][rows], penalty=g["penalty"][rows], window=self.window,
+            max_length=g["max_length"][rows], logit_bias=g["bias"][rows], advance=True, out=eng.tok_buf[rows],
+            history=g["hist"][rows], eos_id=self.eos, pad_id=self.pad, finished=self.finished[rows],
+            length=self.length[rows], unfinished=g["unfinished"] if rows == slice(None) else None,
+            pos=eng.pos32[rows] if eng.fused else None)
+        if not eng.fused:                                   # the generic step's int64 positions: the same rule
+            eng.pos_buf[rows] += (self.finished[rows] == 0).to(torch.int64)
+
+    def _body(self):
+        """Step + sampler.  Under a graph the step's own output is the static
+        logits buffer (returned: the capture keeps it); launched directly, the
+        output is copied into self.logits."""
+        eng = self.eng
+        stepfn = eng._step_rows if eng.fused else eng._step
+        lg = stepfn(eng.tok_buf, eng.pos_buf, eng.states)[:, 0]
+        if not self.use_graph:
+            self.logits.copy_(lg)
+            lg = self.logits
+        self._sample(lg, slice(None))
+        return lg
+
+    def _idle_all(self):
+        eng = self.eng
+        for cs, ss in eng.states:
+            cs.zero_()
+            ss.zero_()
+        eng.tok_buf.fill_(self.pad)
+        eng.pos_buf.zero_()
+        eng.pos32.zero_()
+        self.finished.fill_(1)
+        self.length.zero_()
+        self.g["draw"].zero_()
+
+    def _capture(self):
+        """Once, at open, with every slot idle: warm up on a side stream, put
+        the buffers back, capture, put them back again (as generate does)."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._idle_all()
+                self._body()
+        torch.cuda.current_stream().wait_stream(s)
+        self._idle_all()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            self.logits = self._body()
+        self._idle_all()
+        self.graph = gr
+        self.captures += 1
+        DecodeSession.CAPTURES += 1
+
+    @torch.no_grad()
+    def run(self, n=1):
+        """n tokens for every live slot: n replays of the captured graph (or n
+        direct launches of the same body under decode_mode "eager")."""
+        step = self.graph.replay if self.graph is not None else self._body
+        for _ in range(int(n)):
+            step()
+        self.replays += int(n)
+
+    # -- requests ---------------------------------------------------------------
+    def _check_slot(self, slot):
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.slots:
+            raise ValueError(f"session: slot must be an integer in [0, {self.slots})")
+
+    @torch.no_grad()
+    def admit(self, slot, text_hidden, z_style, *, max_new_tokens, text_mask=None, ref_hidden=None, ref_mask=None,
+              prompt_tokens=None, start_token=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+              repetition_penalty=None, logit_bias=None):
+        """Put one request into an idle slot: unbatched tensors, or tensors
+        with a leading 1.  The arguments mean what they mean in generate();
+        `seed` is the request's own stream seed (no row_seeds expansion).
+        Every check comes first; then the slot's rows are rewritten in place,
+        stream-ordered.  The conditioning [ref ‖ text] is padded to max_keys
+        keys before its K/V projection, so every admission runs the same GEMM
+        shape and a request's K/V does not depend on when or where it was
+        admitted.  A prompt of more than one token is prefilled at batch 1
+        through the scan path and the first token drawn here."""
+        m, eng, g, dev, V = self.m, self.eng, self.g, self.dev, self.V
+        self._check_slot(slot)
+        # -- checks: nothing is touched before the last of them ----------------
+        for name, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("seed", seed),
+                        ("max_new_tokens", max_new_tokens),
+                        ("repetition_penalty", 1.0 if repetition_penalty is None else repetition_penalty)):
+            if not _is_scalar(v):
+                raise ValueError(f"generate: {name} must be a scalar for one request")
+        ctl = DecodeEngine._row_controls(1, [temperature], [top_k], [top_p], [seed], [max_new_tokens],
+                                         None if repetition_penalty is None else [repetition_penalty], self.window)
+        cap = int(ctl["max_length"][0])
+        d = m.token_embed.weight.shape[1]
+
+        def lead(t, dims, name):
+            if t is None:
+                return None
+            if t.dim() == dims - 1:
+                t = t[None]
+            if t.dim() != dims or t.shape[0] != 1:
+                raise ValueError(f"admit: {name} must be one request (unbatched, or a leading 1)")
+            return t
+
+        th = lead(text_hidden, 3, "text_hidden")
+        z = lead(z_style, 2, "z_style")
+        tm, rh, rm = lead(text_mask, 2, "text_mask"), lead(ref_hidden, 3, "ref_hidden"), lead(ref_mask, 2, "ref_mask")
+        if not (th.is_cuda and z.is_cuda):
+            raise RuntimeError("admit runs on the HIP kernels only (no CPU path)")
+        if th.shape[2] != d or (tm is not None and tm.shape[1] != th.shape[1]):
+            raise ValueError("admit: text_hidden must be (T_text, d_model) and text_mask (T_text,)")
+        S = th.shape[1] + (0 if rh is None else rh.shape[1])
+        if S > self.max_keys:
+            raise ValueError(f"admit: {S} conditioning keys exceed the session's max_keys = {self.max_keys}")
+        if S < 1:
+            raise ValueError("admit: the conditioning sequence is empty")
+        pt = prompt_tokens
+        if pt is not None:
+            if pt.dim() == 1:
+                pt = pt[None]
+            if pt.dim() != 2 or pt.shape[0] != 1 or pt.shape[1] < 1:
+                raise ValueError("generate: prompt_tokens must be (Tp,) or (1, Tp) with Tp >= 1")
+        Tp = 1 if pt is None else pt.shape[1]
+        if Tp + cap - 1 > self.P:
+            raise IndexError(f"generate: {Tp} prompt + {cap} new tokens need positions beyond pos_embed "
+                             f"({self.P}) (index out of range in self)")
+        if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (1, V)):
+            raise ValueError("generate: logit_bias must be (V,) or (1, V)")
+        n_tok = m.token_embed.num_embeddings
+        if pt is None:
+            if not 0 <= int(start_token) < n_tok:
+                raise IndexError("generate: start_token out of range of token_embed (index out of range in self)")
+        elif int(pt.min()) < 0 or int(pt.max()) >= n_tok:
+            raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
+        if self.state[slot] != "idle":
+            raise RuntimeError(f"admit: slot {slot} holds a request that has not been taken")
+        # -- conditioning: [ref ‖ text] padded to max_keys, projected, written in place
+        cd, K = self.cd, self.max_keys
+        th, tm = m._concat_ref(th.to(cd), tm, rh, rm, 1, dev)
+        thp = torch.zeros(1, K, d, device=dev, dtype=cd)
+        thp[:, :S] = th
+        keep = torch.zeros(1, K, dtype=torch.bool, device=dev)
+        keep[:, :S] = True if tm is None else tm.to(dev)
+        self.kpm[slot] = ~keep[0]
+        r = slot
+        for l, p in zip(m.layers, eng.ctx["layers"]):
+            kv = torch.addmm(p["bkv"], thp.reshape(-1, d), p["Wkv"].t())           # (max_keys, 2d): one shape, always
+            lin = l.style_mlp[0]
+            gb = torch.tanh(F.linear(z.to(lin.weight.dtype), lin.weight, lin.bias)).to(cd)
+            self._write_cond(p, r, kv[:, :d], kv[:, d:], gb[0, :d], gb[0, d:], l.cross_attn.num_heads)
+        for cs, ss in eng.states:
+            cs[r].zero_()
+            ss[r].zero_()
+        # -- slot state and controls
+        self.length[r:r + 1].zero_()
+        g["draw"][r:r + 1].zero_()
+        for name in ("temperature", "top_k", "top_p", "row_seed", "penalty", "max_length"):
+            g[name][r:r + 1].copy_(ctl[name])
+        if logit_bias is None:
+            g["bias"][r].zero_()
+        else:
+            g["bias"][r].copy_(logit_bias.to(torch.float32).reshape(V))
+        self.finished[r:r + 1].zero_()
+        if Tp > 1:
+            conds = (thp, z, keep, None, None)
+            logits0 = self.pre._prefill(pt.long().to(dev), conds)                   # (1, V); states into self.pre
+            for (cs, ss), (c1, s1) in zip(eng.states, self.pre.states):
+                cs[r].copy_(c1[0])
+                ss[r].copy_(s1[0])
+            eng.pos32[r:r + 1].fill_(Tp - 1)
+            eng.pos_buf[r:r + 1].fill_(Tp - 1)
+            self._sample(logits0, slice(r, r + 1))          # token 0 from the prompt's last logits; pos -> Tp
+        else:
+            eng.tok_buf[r].fill_(int(start_token) if pt is None else 0)
+            if pt is not None:
+                eng.tok_buf[r].copy_(pt[0])
+            eng.pos32[r:r + 1].zero_()
+            eng.pos_buf[r:r + 1].zero_()
+        self.state[slot] = "live"
+
+    def _write_cond(self, p, r, k, v, gamma, beta, H):
+        """Row r of one layer's K / V (and head-major copies) and FiLM rows
+        (and packed images), in place.  k, v (max_keys, d); gamma, beta (d,)."""
+        K, d = k.shape
+        p["k"][r].copy_(k)
+        p["v"][r].copy_(v)
+        if "khm" in p:
+            p["khm"][r].copy_(k.reshape(K, H, d // H).permute(1, 0, 2))
+            p["vhm"][r].copy_(v.reshape(K, H, d // H).permute(1, 0, 2))
+        p["gamma"][r].copy_(gamma)
+        p["beta"][r].copy_(beta)
+        if "gamma_p" in p:                                  # PackedAct.pack's layout: [s, half, g, row, q]
+            for name, row in (("gamma_p", gamma), ("beta_p", beta)):
+                img = p[name].data.view(d // 32, 2, 4, 16, 8)
+                img[:, r // 16, :, r % 16, :].copy_(row.reshape(d // 32, 4, 8))
+
+    def _make_idle(self, r):
+        eng = self.eng
+        z = torch.zeros((), device=self.dev, dtype=self.cd)
+        for l, p in zip(self.m.layers, eng.ctx["layers"]):
+            K, d = p["k"].shape[1:]
+            self._write_cond(p, r, z.expand(K, d), z.expand(K, d), z.expand(d), z.expand(d), l.cross_attn.num_heads)
+        self.kpm[r] = True
+        self.kpm[r, 0] = False
+        self.finished[r:r + 1].fill_(1)
+        eng.tok_buf[r].fill_(self.pad)
+        eng.pos32[r:r + 1].zero_()
+        eng.pos_buf[r:r + 1].zero_()
+
+    def poll(self):
+        """The slots whose request has finished and has not been taken: one
+        copy of finished / length to pinned memory, waited for.  Raises
+        IndexError when a step embedded a token id outside token_embed."""
+        if self.eng.fused:
+            self.eng._post_token_flag(self.dev)
+        self._raw_host.copy_(self._raw, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.eng.check_errors()
+        n = self.slots
+        length = self._raw_host[:8 * n].view(torch.int64)
+        fin = self._raw_host[8 * n:].view(torch.int32)
+        for s in range(n):
+            if self.state[s] == "live" and int(fin[s]) != 0:
+                self.state[s] = "done"
+                self.lengths[s] = int(length[s])
+        return [s for s in range(n) if self.state[s] == "done"]
+
+    @torch.no_grad()
+    def take(self, slot):
+        """The finished request's tokens, (length,) int64, and the slot idle again."""
+        self._check_slot(slot)
+        if self.state[slot] == "live":
+            self.poll()
+        if self.state[slot] != "done":
+            raise RuntimeError(f"take: slot {slot} holds no finished request")
+        toks = self.g["hist"][slot, :self.lengths[slot]].clone()
+        self._make_idle(slot)
+        self.state[slot] = "idle"
+        return toks
+
+
+def _keys(req):
+    th, rh = req["text_hidden"], req.get("ref_hidden")
+    return th.shape[-2] + (0 if rh is None else rh.shape[-2])
+
+
+@torch.no_grad()
+def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
+                      repetition_window=64):
+    """A queue of requests (dicts of DecodeSession.admit's arguments) through
+    one session of `slots` rows by the policy of plan_slots.  Returns the
+    token tensors in request order, the slot each request ran in and the
+    number of replays made.  With eos_id a row may end before its cap: the
+    loop polls, so the slots then differ from plan_slots' (cap-only) answer;
+    no token does."""
+    requests = list(requests)
+    if int(check_every) < 1:
+        raise ValueError("generate_requests: check_every must be >= 1")
+    if not requests:
+        return [], [], 0
+    if max_keys is None:
+        max_keys = max(_keys(r) for r in requests)
+    ses = model.open_session(slots, max_keys, eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window)
+    out, where = [None] * len(requests), [None] * len(requests)
+    left, who = [None] * ses.slots, [None] * ses.slots      # plan_slots' bookkeeping, with the request's index
+    nxt = 0
+    while nxt < len(requests) or any(v is not None for v in left):
+        for s in range(ses.slots):
+            if left[s] is None and nxt < len(requests):
+                req = requests[nxt]
+                ses.admit(s, **req)
+                pt = req.get("prompt_tokens")
+                left[s] = int(req["max_new_tokens"]) - (1 if pt is not None and pt.shape[-1] > 1 else 0)
+                who[s], where[nxt] = nxt, s
+                nxt += 1
+        n = min(int(check_every), max(v for v in left if v is not None))
+        ses.run(n)
+        left = [None if v is None else max(v - n, 0) for v in left]
+        done = ses.poll()
+        if n == 0 and not done:
+            raise RuntimeError("generate_requests: a request passed its cap without finishing")
+        for s in done:
+            out[who[s]] = ses.take(s)
+            left[s] = who[s] = None
+    return out, where, ses.replays

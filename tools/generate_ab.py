@@ -13,7 +13,14 @@ the ragged continuation against the rectangular one (the same graph).
 / top_p=0.9): (a) the scalar path, (b) the per-row path with the same
 settings in every row and no penalty, (c) the per-row path with
 repetition_penalty 1.3 over a window of 64.
-python tools/generate_ab.py [--steps 512] [--ragged | --rows] [--out FILE]"""
+--session runs the continuous-batching leg instead: (1) us per replay of a
+DecodeSession's graph (32 slots, every slot live) against generate()'s
+rows-path graph, same controls, vocabulary 10 and 1024, three interleaved
+repeats; (2) 128 requests with caps uniform in [200, 1000] (fixed seed)
+through generate_requests on 32 slots against static batches of 32 through
+generate(): replays (derived from plan_slots beforehand, and made) and wall
+time.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -130,19 +137,110 @@ def rows_leg(n, dev, lines):
         lines.append(f"vocab {vocab:5d} graphs captured {len(m._engine.gen_graphs)}")
 
 
+def session_leg(n, dev, lines):
+    import time
+
+    import mamba_decoder
+    from mtts.session import plan_slots
+    B = 32
+    lines.append(f"decode session vs generate() rows path, C4 (12L d=1024 B=32 bf16), {n} steps, top_k=50 top_p=0.9, "
+                 "us per token (three interleaved repeats, min first; spread = max - min).  generate() is timed as a "
+                 "call (its per-call host work and final synchronisation spread over the steps), the session as "
+                 "run(n) alone with every slot live")
+    caps = torch.randint(200, 1001, (128,), generator=torch.Generator().manual_seed(11)).tolist()
+    static = sum(max(caps[i:i + B]) for i in range(0, len(caps), B))
+    _, planned = plan_slots(caps, B, 16)
+    for vocab in (10, 1024):
+        c = dict(bench.C2)
+        c["B"] = B
+        torch.manual_seed(0)
+        m = mamba_decoder.MambaTTSDecoder(vocab, d_model=c["d_model"], n_layers=c["n_layers"], n_heads=c["n_heads"],
+                                          d_ff=c["d_ff"], d_style=c["d_style"]).to(dev).eval()
+        m.compute_dtype = torch.bfloat16
+        _, text, z, mask = bench.make_batch(c, dev, 7)
+        kw = dict(top_k=50, top_p=0.9, text_mask=mask, seed=list(range(1, B + 1)), temperature=[1.0] * B)
+        ses = m.open_session(B, text.shape[1], repetition_window=64)
+
+        def gen(penalty):
+            m.generate(text, z, n, repetition_penalty=penalty, repetition_window=64, **kw)
+
+        def fill(penalty):
+            for r in range(B):
+                ses.admit(r, text[r], z[r], text_mask=mask[r], max_new_tokens=n, temperature=1.0, top_k=50,
+                          top_p=0.9, seed=r + 1, repetition_penalty=penalty)
+
+        def drain():
+            for r in ses.poll():
+                ses.take(r)
+
+        def session(penalty):
+            fill(penalty)
+            t = timed(lambda: ses.run(n))
+            drain()
+            return t
+
+        cases = (("(b) generate, per-row path, no penalty", lambda: timed(lambda: gen(None))),
+                 ("(s) session, no penalty", lambda: session(None)),
+                 ("(c) generate, per-row path, penalty 1.3 window 64", lambda: timed(lambda: gen(1.3))),
+                 ("(t) session, penalty 1.3 window 64", lambda: session(1.3)))
+        for _, f in cases:
+            f()                                            # capture / warm up
+        res = [[] for _ in cases]
+        for _ in range(3):
+            for r, (_, f) in zip(res, cases):
+                r.append(f() * 1e3 / n)
+        for i, ((name, _), r) in enumerate(zip(cases, res)):
+            against = "" if i % 2 == 0 else f"  session - generate {min(r) - min(res[i - 1]):+.1f}"
+            lines.append(f"vocab {vocab:5d} {name:50s} {min(r):7.1f} (" + " ".join(f"{v:.1f}" for v in r)
+                         + f")  spread {max(r) - min(r):.1f}" + against)
+            print(lines[-1], flush=True)
+        lines.append(f"vocab {vocab:5d} graphs captured: generate {len(m._engine.gen_graphs)}, session {ses.captures}")
+        # throughput: 128 requests, caps uniform in [200, 1000]
+        reqs = [dict(text_hidden=text[i % B], z_style=z[i % B], text_mask=mask[i % B], max_new_tokens=caps[i],
+                     temperature=1.0, top_k=50, top_p=0.9, seed=i + 1) for i in range(len(caps))]
+
+        def static_batches():
+            made = 0
+            for i in range(0, len(caps), B):
+                toks, _ = m.generate(text, z, caps[i:i + B], top_k=50, top_p=0.9, text_mask=mask,
+                                     temperature=[1.0] * B, seed=list(range(i + 1, i + B + 1)))
+                made += toks.shape[1]
+            return made
+
+        def wall(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = f()
+            torch.cuda.synchronize()
+            return out, time.perf_counter() - t0
+
+        static_batches()                                   # warm up both
+        m.generate_requests(reqs[:B], slots=B, max_keys=text.shape[1], check_every=16)
+        made_s, t_s = wall(static_batches)
+        (toks, _, made_c), t_c = wall(lambda: m.generate_requests(reqs, slots=B, max_keys=text.shape[1],
+                                                                  check_every=16))
+        assert [int(t.numel()) for t in toks] == caps
+        lines.append(f"vocab {vocab:5d} 128 requests, caps uniform in [200, 1000] (sum {sum(caps)}): static batches of "
+                     f"{B}: {made_s} replays (derived {static}), {t_s:.3f} s; session of {B} slots, check_every 16: "
+                     f"{made_c} replays (derived {planned}), {t_c:.3f} s (session open and capture included); "
+                     f"replay ratio {made_c / made_s:.3f} (derived {planned / static:.3f}), wall ratio {t_c / t_s:.3f}")
+        print(lines[-1], flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--ragged", action="store_true", help="run the ragged-prompt leg instead")
     ap.add_argument("--rows", action="store_true", help="run the per-row sampling leg instead")
+    ap.add_argument("--session", action="store_true", help="run the continuous-batching leg instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged or args.rows:
+    if args.ragged or args.rows or args.session:
         lines = []
-        (ragged_leg if args.ragged else rows_leg)(n, dev, lines)
+        (ragged_leg if args.ragged else rows_leg if args.rows else session_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
