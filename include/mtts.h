@@ -392,6 +392,28 @@ typedef struct {
 } MttsAttnQProjArgs;
 int mtts_attention_decode_qproj(const MttsAttnQProjArgs* a, void* stream);
 
+/* Single-query attention over a long key side, split over the keys
+ * (csrc/attn.hip; the decode step against train.py's 5248 conditioning keys).
+ * f as for mtts_attention_fwd with q_len 1 (any kv_len >= 1, either k / v
+ * layout, out and / or out_packed).  Two launches: one workgroup per (batch,
+ * head, chunk of 16384 / head_dim keys) leaves an fp32 partial in the
+ * workspace, then one per (batch, head) sums the row's partials in chunk
+ * order.  The chunk size depends on head_dim alone, so a row's result is the
+ * same bits at any batch size, row index and kv_len.  kv_lens, optional:
+ * (batch) int32 in device memory, row b attends to keys
+ * [0, min(kv_lens[b], kv_len)) only (still subject to key_padding_mask) and
+ * no key at or past that count is read; 0 gives the fully masked row (NaN,
+ * lse -inf).  No atomics; deterministic. */
+typedef struct {
+  MttsAttnFwdArgs f;
+  const int32_t* kv_lens;    /* may be NULL: every row has kv_len keys */
+  void* workspace;           /* mtts_attention_decode_split_workspace() bytes, 4-byte aligned */
+  int64_t workspace_bytes;
+} MttsAttnDecodeSplitArgs;
+
+int64_t mtts_attention_decode_split_workspace(int batch, int heads, int head_dim, int kv_len);
+int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* a, void* stream);
+
 /* Backward: dout -> dq, dk, dv (same dtype as q).  f.out / f.lse must hold
  * the forward's results.  Deterministic (no atomics). */
 typedef struct {

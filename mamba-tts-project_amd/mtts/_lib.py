@@ -157,6 +157,10 @@ class AttnQProjArgs(C.Structure):
                 ("eps", f32), ("d_model", i32)]
 
 
+class AttnDecodeSplitArgs(C.Structure):
+    _fields_ = [("f", AttnFwdArgs), ("kv_lens", vp), ("workspace", vp), ("workspace_bytes", i64)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("f", AttnFwdArgs), ("dout", vp), ("do_bs", i64), ("do_ls", i64),
                 ("dq", vp), ("dq_bs", i64), ("dq_ls", i64), ("dk", vp), ("dk_bs", i64), ("dk_ls", i64),
@@ -207,6 +211,8 @@ _SIGS = {
     "mtts_colsum": ([vp, i32, i32, i32, i64, i32, vp, i64, vp, vp], i32),
     "mtts_attention_fwd": ([C.POINTER(AttnFwdArgs), vp], i32),
     "mtts_attention_decode_qproj": ([C.POINTER(AttnQProjArgs), vp], i32),
+    "mtts_attention_decode_split_workspace": ([i32, i32, i32, i32], i64),
+    "mtts_attention_decode_split": ([C.POINTER(AttnDecodeSplitArgs), vp], i32),
     "mtts_attention_bwd_workspace": ([i32, i32, i32, i32, i32, i32], i64),
     "mtts_attention_bwd": ([C.POINTER(AttnBwdArgs), vp], i32),
     "mtts_adam_chunks": ([i64], i64),
@@ -243,7 +249,8 @@ def lib():
         for sym, what in (("mtts_embed_sum_at", "ragged prompts"),
                           ("mtts_sample_tokens_rows", "per-row sampling"),
                           ("mtts_sample_tokens_slots", "decode sessions"),
-                          ("mtts_gemm_grouped_rounds", "round-filling weight gradients")):
+                          ("mtts_gemm_grouped_rounds", "round-filling weight gradients"),
+                          ("mtts_attention_decode_split", "long-conditioning decode")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "

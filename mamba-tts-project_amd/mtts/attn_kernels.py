@@ -128,6 +128,102 @@ def attention_decode_qproj_packed(x, wq, bq, ln_w, ln_b, eps, k, v, n_heads, kpm
     return yp
 
 
+def decode_split_chunk(hd):
+    """Keys per workgroup of the split-key single-query kernel: what the
+    single-pass decode kernel holds in registers, a function of the head dim
+    alone (csrc/attn.hip attn_decode_split_kernel)."""
+    if hd not in _HEAD_DIMS:
+        raise ValueError(f"head_dim {hd} not supported (need one of {_HEAD_DIMS})")
+    return 16384 // hd
+
+
+def key_counts(keep):
+    """A row's key count: the index of its last kept key + 1, 0 for a row
+    that keeps none.  keep (B, S) bool, True = attend; returns (B,) int32 on
+    keep's device, without a host synchronisation.  Keys below the count may
+    still be masked (the padding of a reference prompt inside [ref ‖ text]);
+    keys at or past it are never read by attention_decode_split."""
+    if keep.dim() != 2 or keep.dtype != torch.bool:
+        raise TypeError("key_counts: keep must be (B, S) bool (True = attend)")
+    B, S = keep.shape
+    if S == 0:
+        return torch.zeros(B, dtype=torch.int32, device=keep.device)
+    idx = torch.arange(1, S + 1, dtype=torch.int32, device=keep.device)
+    return (keep.to(torch.int32) * idx).amax(dim=1)
+
+
+def decode_split_workspace(B, n_heads, hd, S):
+    """Bytes of fp32 partials attention_decode_split needs (at least 4, so
+    that an empty batch still has an address to pass)."""
+    return max(int(L.lib().mtts_attention_decode_split_workspace(B, n_heads, hd, S)), 4)
+
+
+def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=False, want_lse=False, workspace=None):
+    """Single-query attention over a long key side (mtts_attention_decode_split:
+    one workgroup per (batch, head, chunk of decode_split_chunk(hd) keys), then
+    a merge in chunk order).  q (B, d); k / v (B, S, d) channel-last or
+    head-major (B, H, S, hd) contiguous; kpm (B, S) bool, True = ignore;
+    kv_lens (B,) int32 on the device: row b attends to its first kv_lens[b]
+    keys only and reads no other.  Returns the (B, d) output, or its packed
+    activation image (ops.PackedAct; bf16, B <= 32) when `packed`; with
+    want_lse also the (B, H) fp32 log-sum-exp.  workspace: a uint8 device
+    tensor of decode_split_workspace(B, H, hd, S) bytes to keep the partials
+    in (the decode engine holds one per context); None allocates one."""
+    from .ops import PackedAct
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
+    if q.dim() != 2:
+        raise ValueError("attention_decode_split: q must be (B, d)")
+    B, d = q.shape
+    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
+        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("q, k, v must share a dtype")
+    hd = d // n_heads
+    q3 = q[:, None]
+    if not _aligned(q3):
+        q3 = q3.contiguous()
+    out = None if packed else torch.empty(B, 1, d, device=q.device, dtype=q.dtype)
+    yp = PackedAct.empty(B, d, q.device) if packed else None
+    o3 = q3 if out is None else out                         # strides only: no row-major out when packed
+    if k.dim() == 4:   # head-major
+        H, S, hdk = k.shape[1:]
+        if H != n_heads or hdk != hd or k.shape != v.shape or not (k.is_contiguous() and v.is_contiguous()):
+            raise ValueError("attention_decode_split: head-major k / v must be contiguous (B, H, S, hd)")
+        m = _mask_u8(kpm, B, S)
+        a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, o3, None)
+        a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
+    else:
+        k, v = _prep(k), _prep(v)
+        S = k.shape[1]
+        m = _mask_u8(kpm, B, S)
+        a = _fwd_args(q3, k, v, n_heads, m, o3, None)
+    if S < 1:
+        raise ValueError("attention_decode_split: the key side is empty")
+    lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
+    a.lse = L.ptr(lse)
+    a.out = 0 if out is None else out.data_ptr()
+    a.out_packed = None if yp is None else yp.data.data_ptr()
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,) or not kv_lens.is_cuda \
+                or not kv_lens.is_contiguous():
+            raise ValueError(f"attention_decode_split: kv_lens must be ({B},) int32 on the device")
+    sa = L.AttnDecodeSplitArgs()
+    sa.f = a
+    sa.kv_lens = L.ptr(kv_lens)
+    nbytes = decode_split_workspace(B, n_heads, hd, S)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
+    elif ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise ValueError(f"attention_decode_split: workspace must be >= {nbytes} contiguous uint8 bytes on the device")
+    sa.workspace, sa.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.call("mtts_attention_decode_split", sa)
+    res = yp if packed else out[:, 0]
+    return (res, lse) if want_lse else res
+
+
 def attention_fwd(q, k, v, n_heads, kpm=None, want_lse=False):
     """Returns (out (B, T, d) in q's dtype, lse (B, H, T) fp32 or None)."""
     for t in (q, k, v):

@@ -1914,6 +1914,146 @@ void launch_decode_qp(const MttsAttnFwdArgs* a, const QProj& qp, hipStream_t st)
     hipLaunchKernelGGL((attn_decode1_kernel<mtts::bf16_t, HD, 8, true>), grid, dim3(256), 0, st, *a, qp);
 }
 
+// ---------------------------------------------------------------------------
+// Long key sides (the 5248-key conditioning of train.py), split over the key
+// axis: workgroup (b, h, c) owns the CK = 16384 / HD keys of chunk c -- what
+// attn_decode1_kernel<T, HD, 8> holds in registers -- and runs that kernel's
+// single-pass body on them (all K and V of the chunk loaded before any
+// arithmetic, no online rescaling), leaving one fp32 partial (chunk max in
+// log2 units, sum p, HD unnormalised accumulators) in the workspace; the
+// merge launch sums a row's partials in chunk order.  CK depends on the head
+// dim alone, so a row's chunks, and with them every rounding of its result,
+// are the same at any batch size, row index and kv_len.  A row reads only its
+// own n_b = min(kv_lens[b], kv_len) keys: chunks at or past n_b return before
+// any load, key indices past n_b are clamped to the chunk's first key.
+// No atomics, no hand-off inside a launch.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int row_keys(const int32_t* kv_lens, int b, int kv_len) {
+  if (!kv_lens) return kv_len;
+  const int n = kv_lens[b];
+  return n < 0 ? 0 : (n < kv_len ? n : kv_len);
+}
+
+constexpr int split_chunk(int hd) { return 16384 / hd; }
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void attn_decode_split_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens, float* ws,
+                                                                 int nchunk) {
+  constexpr int G = HD / 8, NG = 256 / G, U = 8, CK = NG * U;
+  static_assert(CK == split_chunk(HD), "a chunk is what the single-pass kernel holds in registers");
+  __shared__ float swm[4], swl[4], sacc[4][HD];
+  const int bh = blockIdx.x, chunk = blockIdx.y, b = bh / a.heads, hh = bh % a.heads;
+  const int n = row_keys(kv_lens, b, a.kv_len), k0 = chunk * CK;
+  if (k0 >= n) return;   // uniform over the workgroup; before any load or barrier
+  const int g = threadIdx.x / G, gl = threadIdx.x % G, d0 = gl * 8, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const float c = a.scale * kLog2e;
+  float q[8];
+  ld8((const T*)a.q + b * a.q_bs + hh * HD + d0, q);
+  const int64_t hs = a.kv_hs ? a.kv_hs : HD;
+  const T* kb = (const T*)a.k + b * a.k_bs + hh * hs + d0;
+  const T* vb = (const T*)a.v + b * a.v_bs + hh * hs + d0;
+  const uint8_t* mb = a.key_padding_mask ? a.key_padding_mask + b * a.mask_bs : (const uint8_t*)a.q;
+  const uint32_t mmask = a.key_padding_mask ? 0xffu : 0u;
+  float kx[U][8], vx[U][8];
+  bool ok[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = k0 + g + u * NG;
+    const int jj = j < n ? j : k0;   // k0 < n: a key of the row
+    ld8(kb + (int64_t)jj * a.k_ls, kx[u]);
+    ld8(vb + (int64_t)jj * a.v_ls, vx[u]);
+    ok[u] = j < n && ((uint32_t)mb[a.key_padding_mask ? jj : 0] & mmask) == 0;
+  }
+  float sc[U], m = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float sv = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sv = fmaf(q[e], kx[u][e], sv);
+    sv = group_sum<G>(sv, lane);
+    sc[u] = ok[u] ? sv * c : -INFINITY;
+    m = fmaxf(m, sc[u]);
+  }
+  m = groups_max<G>(m, lane);
+  if (lane == 0) swm[wave] = m;
+  block_sync();
+  const float M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
+  float l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float p = ok[u] ? exp2f(sc[u] - M) : 0.f;
+    l += p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vx[u][e], acc[e]);
+  }
+  l = groups_sum<G>(l, lane);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = groups_sum<G>(acc[e], lane);
+  if (lane < G) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sacc[wave][d0 + e] = acc[e];
+    if (gl == 0) swl[wave] = l;
+  }
+  block_sync();
+  if (threadIdx.x < HD) {
+    // every key of the chunk masked: M = -inf, sum p = 0, accumulators 0
+    float* pw = ws + ((int64_t)bh * nchunk + chunk) * (HD + 2);
+    if (threadIdx.x == 0) pw[0] = M, pw[1] = (swl[0] + swl[1]) + (swl[2] + swl[3]);
+    pw[2 + threadIdx.x] = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
+  }
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(HD < 64 ? 64 : HD) void attn_decode_merge_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens,
+                                                                               const float* ws, int nchunk) {
+  constexpr int CK = split_chunk(HD);
+  const int bh = blockIdx.x, b = bh / a.heads, hh = bh % a.heads, t = threadIdx.x;
+  if (t >= HD) return;
+  const int n = row_keys(kv_lens, b, a.kv_len), nc = (n + CK - 1) / CK;   // the chunks the first launch wrote
+  const float* pw = ws + (int64_t)bh * nchunk * (HD + 2);
+  float M = -INFINITY;
+  for (int i = 0; i < nc; ++i) M = fmaxf(M, pw[(int64_t)i * (HD + 2)]);
+  float L = 0.f, o = 0.f;
+  for (int i = 0; i < nc; ++i) {
+    const float* pi = pw + (int64_t)i * (HD + 2);
+    const float f = pi[0] == -INFINITY ? 0.f : exp2f(pi[0] - M);   // a fully masked chunk enters with factor 0
+    L += pi[1] * f;
+    o += pi[2 + t] * f;
+  }
+  // no key (n = 0) or every key masked: L = 0 -> 0/0 = NaN (torch MHA), lse = -inf
+  if (a.out) mtts::stf((T*)a.out + b * a.o_bs + hh * HD + t, o / L);
+  if constexpr (sizeof(T) == 2) {
+    if (a.out_packed) ((mtts::bf16_t*)a.out_packed)[mtts::xpk_index(b, hh * HD + t)] = mtts::f2bf(o / L);
+  }
+  if (a.lse && t == 0) a.lse[(int64_t)b * a.heads + hh] = M == -INFINITY ? -INFINITY : (M + log2f(L)) * kLn2;
+}
+
+template <typename T, int HD>
+void launch_decode_split(const MttsAttnFwdArgs* a, const int32_t* kv_lens, float* ws, hipStream_t st) {
+  constexpr int CK = split_chunk(HD);
+  const int nchunk = (a->kv_len + CK - 1) / CK;
+  const int rows = a->batch * a->heads;
+  hipLaunchKernelGGL((attn_decode_split_kernel<T, HD>), dim3(rows, nchunk), dim3(256), 0, st, *a, kv_lens, ws, nchunk);
+  hipLaunchKernelGGL((attn_decode_merge_kernel<T, HD>), dim3(rows), dim3(HD < 64 ? 64 : HD), 0, st, *a, kv_lens,
+                     (const float*)ws, nchunk);
+}
+
+template <typename T>
+void dispatch_decode_split(const MttsAttnFwdArgs* a, const int32_t* kv_lens, float* ws, hipStream_t st) {
+  switch (a->head_dim) {
+    case 16: launch_decode_split<T, 16>(a, kv_lens, ws, st); break;
+    case 32: launch_decode_split<T, 32>(a, kv_lens, ws, st); break;
+    case 64: launch_decode_split<T, 64>(a, kv_lens, ws, st); break;
+    default: launch_decode_split<T, 128>(a, kv_lens, ws, st); break;
+  }
+}
+
+int64_t decode_split_bytes(int batch, int heads, int head_dim, int kv_len) {
+  const int ck = split_chunk(head_dim);
+  return (int64_t)batch * heads * ((kv_len + ck - 1) / ck) * (head_dim + 2) * 4;
+}
+
 template <typename T>
 void dispatch_decode(const MttsAttnFwdArgs* a, hipStream_t st) {
   switch (a->head_dim) {
@@ -2080,6 +2220,42 @@ extern "C" int mtts_attention_decode_qproj(const MttsAttnQProjArgs* q, void* str
   if (a.head_dim == 64) launch_decode_qp<64>(&a, qp, st);
   else launch_decode_qp<128>(&a, qp, st);
   MTTS_LAUNCH_CHECK("attention_decode_qproj");
+  return MTTS_OK;
+}
+
+extern "C" int64_t mtts_attention_decode_split_workspace(int batch, int heads, int head_dim, int kv_len) {
+  if (batch < 0 || heads <= 0 || kv_len < 0 || (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128))
+    return 0;
+  return decode_split_bytes(batch, heads, head_dim, kv_len);
+}
+
+extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, void* stream) {
+  MTTS_CHECK(s, "attention_decode_split: null args");
+  const MttsAttnFwdArgs& a = s->f;
+  MTTS_CHECK(a.q_len == 1, "attention_decode_split: q_len %d (the single-query kernels take q_len 1)", a.q_len);
+  MTTS_CHECK(a.out || a.out_packed, "attention_decode_split: null out and out_packed");
+  {   // check_fwd with the packed image standing in for a missing row-major out
+    MttsAttnFwdArgs c = a;
+    if (!c.out) { c.out = c.out_packed; c.o_bs = c.o_ls = 0; }
+    int rc = check_fwd(&c, "attention_decode_split");
+    if (rc) return rc;
+  }
+  MTTS_CHECK(a.kv_len >= 1, "attention_decode_split: kv_len %d must be >= 1", a.kv_len);
+  MTTS_CHECK(a.kv_hs % 8 == 0 && a.kv_hs >= 0, "attention_decode_split: kv_hs must be a multiple of 8 elements");
+  MTTS_CHECK(!a.out_packed || (a.dtype == MTTS_BF16 && a.batch <= 32 && (a.heads * a.head_dim) % 32 == 0),
+             "attention_decode_split: out_packed needs bf16, batch <= 32 and heads * head_dim %% 32 == 0 "
+             "(dtype %d, batch %d, d %d)", a.dtype, a.batch, a.heads * a.head_dim);
+  if (a.batch == 0) return MTTS_OK;
+  const int64_t need = decode_split_bytes(a.batch, a.heads, a.head_dim, a.kv_len);
+  MTTS_CHECK(s->workspace && ((uintptr_t)s->workspace & 3) == 0 && s->workspace_bytes >= need,
+             "attention_decode_split: workspace of %lld bytes, need %lld (4-byte aligned, "
+             "mtts_attention_decode_split_workspace)", (long long)(s->workspace ? s->workspace_bytes : 0), (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  if (a.dtype == MTTS_BF16)
+    dispatch_decode_split<bf16_t>(&a, s->kv_lens, (float*)s->workspace, st);
+  else
+    dispatch_decode_split<float>(&a, s->kv_lens, (float*)s->workspace, st);
+  MTTS_LAUNCH_CHECK("attention_decode_split");
   return MTTS_OK;
 }
 

@@ -19,6 +19,10 @@ Engine path (inference only: torch.no_grad, HIP tensors):
   * the <= 32-row projections (in/x/dt/out_proj, q/out_proj, FFN, head) on
     the HIP skinny GEMM of csrc/rows.hip (bias + GELU fused) for bf16;
   * dt_proj fused into the selective state update (B / C read in place);
+  * a key side past the single-pass range (decode_split_chunk(hd) keys; the
+    5248 keys of train.py's conditioning) on the split-key kernel
+    (attention_decode_split) from every step, packed included, each row
+    reading its own key count ctx["kv_lens"] = key_counts(keep) only;
   * optional hipGraph capture of the whole step (static token / position /
     state buffers): replay costs one launch instead of ~25 per layer.
   * generate(): the loop around the step on the device -- one hipGraph of
@@ -45,7 +49,8 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import ops
 from .embed import _err_flag, embed_sum
-from .attn_kernels import attention, attention_decode_packed, attention_decode_qproj_packed
+from .attn_kernels import (attention, attention_decode_packed, attention_decode_qproj_packed, attention_decode_split,
+                           decode_split_chunk, decode_split_workspace, key_counts)
 from .linear import cast_scope, cast_weight
 
 
@@ -121,7 +126,12 @@ class DecodeEngine:
                # step (profiles/r05_decode_ab_fuse_q.txt) -- every (batch, head)
                # workgroup re-reads its head's Wq rows (256 KiB) from L2, 64 MiB
                # per layer against 2 MiB for one projection over the 32 rows
-               "fuse_q": False}
+               "fuse_q": False,
+               # key sides past the single-pass range (decode_split_chunk(hd) keys) on the
+               # split-key kernel (mtts_attention_decode_split), which keeps the packed
+               # step on and reads a row's own key count only; off: the serial
+               # attn_decode_kernel under the unpacked step (profiles/decode_long_keys.txt)
+               "split_keys": True}
 
     def __init__(self, model, use_graph=True, use_rows=True):
         self.m = model
@@ -188,7 +198,9 @@ class DecodeEngine:
                 dt_bias=mm.dt_proj.bias.detach().float().contiguous(),
             ))
         dev = text_hidden.device
-        return dict(B=B, kpm=kpm, layers=layers, cd=cd,
+        # the split-key routing is latched here, with the context: _xpk_ok and every later step agree on it
+        return dict(B=B, kpm=kpm, kv_lens=None if kpm is None else key_counts(~kpm), layers=layers, cd=cd,
+                    split=bool(self.OPTIONS["split_keys"]), split_ws=None,
                     tok_w=m.token_embed.weight.detach().float().contiguous(),
                     pos_w=m.pos_embed.weight.detach().float().contiguous(),
                     q0_w=torch.zeros(1, d, device=dev), q0_id=torch.zeros(1, device=dev, dtype=torch.int32),
@@ -279,16 +291,42 @@ class DecodeEngine:
                                  xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"])
             x = ops.gemm_rows(y, w(p, "Wout"), res=x)
             q = ops.gemm_rows(x, w(p, "Wq"), p["bq"], ln=ln(l.norm_cross))
-            o = attention(q[:, None], p["k"], p["v"], l.cross_attn.num_heads, c["kpm"])[:, 0]
+            o = self._cross(q, p["k"], p["v"], l.cross_attn.num_heads)
             x = ops.gemm_rows(o, w(p, "Wo"), p["bo"], res=x)
             f = ops.gemm_rows(x, w(p, "W1"), p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma"], p["beta"]))
             x = ops.gemm_rows(f, w(p, "W2"), p["b2"], res=x)
         return ops.gemm_rows(x, w(c, "Wh"), c["bh"], ln=ln(m.norm_out))[:, None]
 
+    def _split(self, S, hd):
+        """A key side of S keys goes to the split-key kernel: past the
+        single-pass range, with OPTIONS["split_keys"] on when the context
+        was built.  A head dim no attention kernel takes is not this
+        predicate's to refuse: False, and the attention call raises."""
+        return self.ctx["split"] and hd in (16, 32, 64, 128) and S > decode_split_chunk(hd)
+
+    def _cross_split(self, q, k, v, H, packed=False):
+        """The split-key kernel with the context's key counts and its
+        workspace: one allocation per context (every layer's partials have
+        the same shape and the layers run in turn on one stream)."""
+        c = self.ctx
+        S = k.shape[2] if k.dim() == 4 else k.shape[1]
+        need = decode_split_workspace(q.shape[0], H, q.shape[1] // H, S)
+        if c["split_ws"] is None or c["split_ws"].numel() < need:
+            c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
+        return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed, workspace=c["split_ws"])
+
+    def _cross(self, q, k, v, H):
+        """The row-major steps' cross-attention of q (B, d): the split-key
+        kernel on a long key side, else the single-query kernels of
+        mtts_attention_fwd."""
+        if self._split(k.shape[1], q.shape[1] // H):
+            return self._cross_split(q, k, v, H)
+        return attention(q[:, None], k, v, H, self.ctx["kpm"])[:, 0]
+
     def _xpk_ok(self):
         """Every projection packed and every operand shape the packed
-        activation images take (K, N % 32; short key side): the step of
-        _step_xpk applies."""
+        activation images take (K, N % 32; a key side the single-pass or the
+        split-key kernel takes): the step of _step_xpk applies."""
         if not self.OPTIONS["xpacked"]:
             return False
         c = self.ctx
@@ -299,7 +337,8 @@ class DecodeEngine:
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
             if (any(p[k].shape[0] % 32 or p[k].shape[1] % 32 for k in names)
-                    or p["k"].shape[1] > 8 * (256 // (hd // 8)) or l.mamba.d_inner % 32):
+                    or (p["k"].shape[1] > 8 * (256 // (hd // 8)) and not self._split(p["k"].shape[1], hd))
+                    or l.mamba.d_inner % 32):
                 return False
         for l, p in zip(self.m.layers, c["layers"]):   # head-major K / V: one contiguous block per (b, h)
             H = l.cross_attn.num_heads
@@ -353,7 +392,11 @@ class DecodeEngine:
                                                   p["vhm"], l.cross_attn.num_heads, c["kpm"])
             else:
                 q = ops.gemm_rows(xp, p["Wq_p"], p["bq"], ln=ln(l.norm_cross))
-                o = attention_decode_packed(q, p["khm"], p["vhm"], l.cross_attn.num_heads, c["kpm"])
+                H = l.cross_attn.num_heads
+                if self._split(p["khm"].shape[2], p["khm"].shape[3]):   # long key side: chunks of the row's own keys
+                    o = self._cross_split(q, p["khm"], p["vhm"], H, packed=True)
+                else:
+                    o = attention_decode_packed(q, p["khm"], p["vhm"], H, c["kpm"])
             x, xp = ops.gemm_rows(o, p["Wo_p"], p["bo"], res=x, packed_out="also")
             f = ops.gemm_rows(xp, p["W1_p"], p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma_p"], p["beta_p"]),
                               packed_out="only")
@@ -385,7 +428,7 @@ class DecodeEngine:
             h_m = mm_(y, p["Wout"])
             h, x = ops.layer_norm(h_m, l.norm_cross.weight, l.norm_cross.bias, l.norm_cross.eps, res=x)
             q = mm_(h, p["Wq"], p["bq"])
-            o = attention(q[:, None], p["k"], p["v"], l.cross_attn.num_heads, c["kpm"])[:, 0]
+            o = self._cross(q, p["k"], p["v"], l.cross_attn.num_heads)
             a = mm_(o, p["Wo"], p["bo"])
             h, x = ops.layer_norm(a, l.norm_ff.weight, l.norm_ff.bias, l.norm_ff.eps, res=x,
                                   gamma=p["gamma"], beta=p["beta"], rows_per_group=1)

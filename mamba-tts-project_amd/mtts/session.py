@@ -6,9 +6,10 @@ reached its cap idles until the longest one is done.  A Mamba decoder keeps
 O(1) state per row, so a finished row can be handed to the next request at
 once.  DecodeSession keeps everything a request owns as one row of static
 device buffers -- its conditioning K/V over `max_keys` keys, key-padding mask,
-FiLM rows, conv / SSM states, token, position, sampler controls, history --
-and replays ONE captured graph of the engine's decode step plus the slot form
-of the sampler (ops.sample_tokens_slots: the history column is the row's own
+key count (all the split-key attention reads of a long key side), FiLM rows,
+conv / SSM states, token, position, sampler controls, history -- and replays
+ONE captured graph of the engine's decode step plus the slot form of the
+sampler (ops.sample_tokens_slots: the history column is the row's own
 draw count, finished rows keep their tokens and their position).  Admitting a
 request rewrites its slot's rows in place, stream-ordered; no admission,
 control value or seed captures again.  A request's random stream is a function
@@ -24,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .attn_kernels import key_counts
 from .decode import DecodeEngine, _is_scalar
 from .linear import cast_weight
 
@@ -91,6 +93,9 @@ class DecodeSession:
         ctx = eng._build_ctx(torch.zeros(slots, max_keys, d, device=dev, dtype=cd),
                              torch.zeros(slots, ds, device=dev), keep, None, None, cd)
         self.kpm = ctx["kpm"]                               # (slots, max_keys) bool, True = ignore: rewritten in place
+        # (slots,) int32 key counts the captured step's split-key attention reads: an idle slot's only key is key 0
+        self.kv_lens = ctx["kv_lens"]
+        self.kv_lens.fill_(1)
         for l, p in zip(m.layers, ctx["layers"]):
             ca = l.cross_attn
             p["Wkv"] = cast_weight(ca.in_proj_weight, cd)[d:]
@@ -286,6 +291,7 @@ class DecodeSession:
         keep = torch.zeros(1, K, dtype=torch.bool, device=dev)
         keep[:, :S] = True if tm is None else tm.to(dev)
         self.kpm[slot] = ~keep[0]
+        self.kv_lens[slot:slot + 1].copy_(key_counts(keep))  # as generate() derives it from the same mask
         r = slot
         for l, p in zip(m.layers, eng.ctx["layers"]):
             kv = torch.addmm(p["bkv"], thp.reshape(-1, d), p["Wkv"].t())           # (max_keys, 2d): one shape, always
@@ -346,6 +352,7 @@ class DecodeSession:
             self._write_cond(p, r, z.expand(K, d), z.expand(K, d), z.expand(d), z.expand(d), l.cross_attn.num_heads)
         self.kpm[r] = True
         self.kpm[r, 0] = False
+        self.kv_lens[r:r + 1].fill_(1)
         self.finished[r:r + 1].fill_(1)
         eng.tok_buf[r].fill_(self.pad)
         eng.pos32[r:r + 1].zero_()

@@ -20,7 +20,13 @@ repeats; (2) 128 requests with caps uniform in [200, 1000] (fixed seed)
 through generate_requests on 32 slots against static batches of 32 through
 generate(): replays (derived from plan_slots beforehand, and made) and wall
 time.
-python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session] [--out FILE]"""
+--long-keys runs the long-conditioning leg instead (--steps 256): us per token
+of a session with every slot live at train.py's widths (8 layers, d_model 512,
+max_keys 5248; 1, 8 and 32 slots) and at C4's (max_keys 1024, 32 slots), (p)
+with the parent's routing (DecodeEngine.OPTIONS["split_keys"] off), (s) on the
+split-key kernel with every request at max_keys, (r) on it with request key
+counts uniform in [600, max_keys]; three interleaved repeats.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -227,20 +233,86 @@ def session_leg(n, dev, lines):
         print(lines[-1], flush=True)
 
 
+def long_keys_leg(n, dev, lines):
+    """Decode at the conditioning lengths the model has: a session with every
+    slot live, us per token, (p) the parent's routing (OPTIONS["split_keys"]
+    off: the unpacked step and the serial single-query kernel), (s) the
+    split-key kernel with every request at max_keys, (r) the split-key kernel
+    with request key counts uniform in [600, max_keys] (fixed seed)."""
+    import mamba_decoder
+    from mtts.decode import DecodeEngine
+    vocab = 1024
+    lines.append(f"decode over long conditioning, bf16, vocab {vocab}, {n} steps, top_k=50 top_p=0.9, every slot live, "
+                 "us per token (three interleaved repeats in one process, min first; spread = max - min).  (p) parent "
+                 "routing (split_keys off), (s) split-key kernel, every request at max_keys, (r) split-key kernel, "
+                 "key counts uniform in [600, max_keys] (seed 5)")
+    shapes = (("train.py widths (8L d=512 8 heads)", dict(n_layers=8, d_model=512, n_heads=8), 5248, (1, 8, 32)),
+              ("C4 widths (12L d=1024 8 heads)", dict(n_layers=12, d_model=1024, n_heads=8), 1024, (32,)))
+    for name, width, max_keys, slot_counts in shapes:
+        torch.manual_seed(0)
+        m = mamba_decoder.MambaTTSDecoder(vocab, d_ff=2048, d_style=256, **width).to(dev).eval()
+        m.compute_dtype = torch.bfloat16
+        d = width["d_model"]
+        for slots in slot_counts:
+            g = torch.Generator().manual_seed(5)
+            text = torch.randn(slots, max_keys, d, generator=g).to(dev)
+            z = torch.randn(slots, 256, generator=g).to(dev)
+            counts = torch.randint(600, max_keys + 1, (slots,), generator=g).tolist()
+            ses = {}
+            for leg, on in (("p", False), ("s", True), ("r", True)):   # the routing is fixed at capture
+                DecodeEngine.OPTIONS["split_keys"] = on
+                try:
+                    ses[leg] = m.open_session(slots, max_keys, repetition_window=64)
+                finally:
+                    DecodeEngine.OPTIONS["split_keys"] = True
+            assert ses["s"].eng.xpk and ses["r"].eng.xpk and not ses["p"].eng.xpk
+
+            def run(leg):
+                s = ses[leg]
+                for r in range(slots):
+                    keys = counts[r] if leg == "r" else max_keys
+                    s.admit(r, text[r, :keys], z[r], max_new_tokens=n, temperature=1.0, top_k=50, top_p=0.9,
+                            seed=r + 1)
+                t = timed(lambda: s.run(n))
+                for r in s.poll():
+                    s.take(r)
+                return t * 1e3 / n
+
+            for leg in ses:
+                run(leg)                                       # warm up
+            res = {leg: [] for leg in ses}
+            for _ in range(3):
+                for leg in ses:
+                    res[leg].append(run(leg))
+            mean = sum(counts) / slots
+            for leg, what in (("p", "(p) parent routing"), ("s", "(s) split, all at max_keys"),
+                              ("r", f"(r) split, key counts mean {mean:.0f}")):
+                v = res[leg]
+                against = "" if leg == "p" else f"  vs (p) {min(v) - min(res['p']):+.1f}"
+                lines.append(f"{name}, max_keys {max_keys}, {slots:2d} slots  {what:36s} {min(v):8.1f} ("
+                             + " ".join(f"{x:.1f}" for x in v) + f")  spread {max(v) - min(v):.1f}" + against)
+                print(lines[-1], flush=True)
+            del ses
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--ragged", action="store_true", help="run the ragged-prompt leg instead")
     ap.add_argument("--rows", action="store_true", help="run the per-row sampling leg instead")
     ap.add_argument("--session", action="store_true", help="run the continuous-batching leg instead")
+    ap.add_argument("--long-keys", action="store_true", help="run the long-conditioning decode leg instead "
+                    "(profiles/decode_long_keys.txt: --steps 256)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged or args.rows or args.session:
+    if args.ragged or args.rows or args.session or args.long_keys:
         lines = []
-        (ragged_leg if args.ragged else rows_leg if args.rows else session_leg)(n, dev, lines)
+        (ragged_leg if args.ragged else rows_leg if args.rows else session_leg if args.session
+         else long_keys_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
