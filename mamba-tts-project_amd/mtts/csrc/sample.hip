@@ -45,9 +45,18 @@
 // row keeps its history until the host has taken it, and the launch behind
 // the sampler advances the positions of the unfinished rows only.  One more
 // instantiation (kSlots); the other two compile none of it.
+//
+// The host side is one front end for the three entry points: the argument
+// checks they share (check_sample_args, with the per-row and slot forms' own
+// in check_sample_rows_args), one dtype x wave-count launch switch and one
+// launch behind the sampler (launch_sample, sample_advance_kernel<kSlots>).
+// An entry point holds its name and the few checks that are its alone.
 #include "common.h"
 
 #include <math.h>
+
+#include <string>
+#include <type_traits>
 
 namespace mtts {
 namespace {
@@ -352,6 +361,10 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
 
 // Behind the sampler: count the unfinished rows and advance the counters
 // (pos_rows > 0: `pos` holds that many per-row positions, all moved in lockstep).
+// kGateOnFinished, the slot form's: a per-row position moves only when its row
+// is unfinished after the draw, so a row idling past its end stays inside
+// pos_embed however long its slot waits for a request.
+template <bool kGateOnFinished>
 __global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* step, int* pos, const int* finished,
                                                                         int rows, int* unfinished, int advance,
                                                                         int pos_rows) {
@@ -370,33 +383,67 @@ __global__ __launch_bounds__(kSampleThreads) void sample_advance_kernel(int* ste
     }
   }
   if (advance && pos && pos_rows > 0)
-    for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads) pos[r] += 1;
+    for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads)
+      if (!kGateOnFinished || !finished || finished[r] == 0) pos[r] += 1;
 }
 
-// The slot form's launch behind the sampler: as above, but a per-row position
-// moves only when its row is unfinished after the draw, so a row idling past
-// its end stays inside pos_embed however long its slot waits for a request.
-__global__ __launch_bounds__(kSampleThreads) void sample_advance_slots_kernel(int* step, int* pos,
-                                                                              const int* finished, int rows,
-                                                                              int* unfinished, int advance,
-                                                                              int pos_rows) {
-  __shared__ uint64_t slots[2][4];
-  int phase = 0;
-  uint32_t done = 0;
-  if (unfinished) {
-    for (int r = threadIdx.x; r < rows; r += kSampleThreads) done += finished[r] != 0 ? 1u : 0u;
-    done = block_red<4>(done, OpSum(), slots, phase);
+// ---- host side: one front end for the three entry points --------------------
+// Each helper returns the status of its first failing check (MTTS_CHECK returns
+// from the function it stands in) and the entry point hands it on; `name` is
+// the entry point's, so every message keeps its prefix, and the checks fire in
+// the order they always had: null pointers, [per-row arrays], dtype, sizes,
+// strides, [the form's own: `form_checks`], ids, history, unfinished.
+template <typename A, typename F>
+int check_sample_args(const A* a, const char* name, F form_checks) {
+  MTTS_CHECK(a && a->logits && a->tokens, "%s: null pointer", name);
+  if constexpr (std::is_same_v<A, MttsSampleRowsArgs>)
+    MTTS_CHECK(a->temperature && a->top_k && a->top_p && a->seed && a->draw,
+               "%s: temperature, top_k, top_p, seed and draw are required", name);
+  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "%s: dtype must be f32 or bf16", name);
+  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24), "%s: rows=%d vocab=%d out of range", name,
+             a->rows, a->vocab);
+  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
+             "%s: row stride below vocab", name);
+  if (const int s = form_checks()) return s;
+  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
+             "%s: pad_id=%d / eos_id=%d outside the vocabulary", name, a->pad_id, a->eos_id);
+  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols), "%s: bad history shape", name);
+  MTTS_CHECK(!a->unfinished || a->finished, "%s: unfinished needs finished", name);
+  return MTTS_OK;
+}
+
+// The per-row and slot forms: the checks above around their window and length-cap rules.
+int check_sample_rows_args(const MttsSampleRowsArgs* a, const char* name) {
+  return check_sample_args(a, name, [=]() -> int {
+    MTTS_CHECK(a->window >= 0 && a->window <= MTTS_SAMPLE_WINDOW_MAX, "%s: window=%d outside [0, %d]", name,
+               a->window, MTTS_SAMPLE_WINDOW_MAX);
+    MTTS_CHECK(a->window == 0 || a->history, "%s: window=%d needs history", name, a->window);
+    MTTS_CHECK(!a->max_length || (a->finished && a->length), "%s: max_length needs finished and length", name);
+    return MTTS_OK;
+  });
+}
+
+// The sampler for P's form (one wave up to kSampleWaveV entries, else four) and,
+// when asked for, the launch behind it.
+template <typename P, typename A>
+int launch_sample(const A* a, const char* name, hipStream_t st) {
+  P prm;
+  prm.a = *a;
+  const bool f32 = a->dtype == MTTS_F32;
+  if (a->vocab <= kSampleWaveV) {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, P>), dim3(a->rows), dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, P>), dim3(a->rows), dim3(64), 0, st, prm);
+  } else {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 4, P>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 4, P>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
   }
-  if (threadIdx.x == 0) {
-    if (unfinished) *unfinished = rows - (int)done;
-    if (advance) {
-      if (step) *step += 1;
-      if (pos && pos_rows <= 0) *pos += 1;
-    }
+  MTTS_LAUNCH_CHECK(name);
+  if (a->advance || a->unfinished) {
+    hipLaunchKernelGGL(sample_advance_kernel<P::kSlots>, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos,
+                       a->finished, a->rows, a->unfinished, a->advance, a->pos_rows);
+    MTTS_LAUNCH_CHECK((std::string(name) + " (advance)").c_str());
   }
-  if (advance && pos && pos_rows > 0)
-    for (int r = threadIdx.x; r < pos_rows; r += kSampleThreads)
-      if (!finished || finished[r] == 0) pos[r] += 1;
+  return MTTS_OK;
 }
 
 }  // namespace
@@ -405,125 +452,31 @@ __global__ __launch_bounds__(kSampleThreads) void sample_advance_slots_kernel(in
 using namespace mtts;
 
 extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
-  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens: null pointer");
-  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens: dtype must be f32 or bf16");
-  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24), "sample_tokens: rows=%d vocab=%d out of range",
-             a->rows, a->vocab);
-  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
-             "sample_tokens: row stride below vocab");
-  MTTS_CHECK(a->temperature >= 0.f, "sample_tokens: temperature=%f must be >= 0", (double)a->temperature);
-  MTTS_CHECK(a->top_k >= 0, "sample_tokens: top_k=%d must be >= 0", a->top_k);
-  MTTS_CHECK(a->top_p > 0.f && a->top_p <= 1.f, "sample_tokens: top_p=%f must be in (0, 1]", (double)a->top_p);
-  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
-             "sample_tokens: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
-  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols), "sample_tokens: bad history shape");
-  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens: unfinished needs finished");
-  MTTS_CHECK(!a->advance || a->step, "sample_tokens: advance needs step");
-  MTTS_CHECK(a->pos_rows >= 0, "sample_tokens: pos_rows=%d must be >= 0", a->pos_rows);
-  hipStream_t st = (hipStream_t)stream;
-  SampleParams prm;
-  prm.a = *a;
-  const bool f32 = a->dtype == MTTS_F32;
-  if (a->vocab <= kSampleWaveV) {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleParams>), dim3(a->rows), dim3(64), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleParams>), dim3(a->rows), dim3(64), 0, st, prm);
-  } else {
-    if (f32)
-      hipLaunchKernelGGL((sample_kernel<float, 4, SampleParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-    else
-      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-  }
-  MTTS_LAUNCH_CHECK("sample_tokens");
-  if (a->advance || a->unfinished) {
-    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
-                       a->rows, a->unfinished, a->advance, a->pos_rows);
-    MTTS_LAUNCH_CHECK("sample_tokens (advance)");
-  }
-  return MTTS_OK;
+  const char* const name = "sample_tokens";
+  const int s = check_sample_args(a, name, [=]() -> int {
+    MTTS_CHECK(a->temperature >= 0.f, "%s: temperature=%f must be >= 0", name, (double)a->temperature);
+    MTTS_CHECK(a->top_k >= 0, "%s: top_k=%d must be >= 0", name, a->top_k);
+    MTTS_CHECK(a->top_p > 0.f && a->top_p <= 1.f, "%s: top_p=%f must be in (0, 1]", name, (double)a->top_p);
+    return MTTS_OK;
+  });
+  if (s) return s;
+  MTTS_CHECK(!a->advance || a->step, "%s: advance needs step", name);
+  MTTS_CHECK(a->pos_rows >= 0, "%s: pos_rows=%d must be >= 0", name, a->pos_rows);
+  return launch_sample<SampleParams>(a, name, (hipStream_t)stream);
 }
 
 extern "C" int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream) {
-  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens_rows: null pointer");
-  MTTS_CHECK(a->temperature && a->top_k && a->top_p && a->seed && a->draw,
-             "sample_tokens_rows: temperature, top_k, top_p, seed and draw are required");
-  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens_rows: dtype must be f32 or bf16");
-  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24),
-             "sample_tokens_rows: rows=%d vocab=%d out of range", a->rows, a->vocab);
-  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
-             "sample_tokens_rows: row stride below vocab");
-  MTTS_CHECK(a->window >= 0 && a->window <= MTTS_SAMPLE_WINDOW_MAX, "sample_tokens_rows: window=%d outside [0, %d]",
-             a->window, MTTS_SAMPLE_WINDOW_MAX);
-  MTTS_CHECK(a->window == 0 || a->history, "sample_tokens_rows: window=%d needs history", a->window);
-  MTTS_CHECK(!a->max_length || (a->finished && a->length), "sample_tokens_rows: max_length needs finished and length");
-  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
-             "sample_tokens_rows: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
-  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols),
-             "sample_tokens_rows: bad history shape");
-  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens_rows: unfinished needs finished");
-  MTTS_CHECK(!a->advance || a->step, "sample_tokens_rows: advance needs step");
-  MTTS_CHECK(a->pos_rows >= 0, "sample_tokens_rows: pos_rows=%d must be >= 0", a->pos_rows);
-  hipStream_t st = (hipStream_t)stream;
-  SampleRowsParams prm;
-  prm.a = *a;
-  const bool f32 = a->dtype == MTTS_F32;
-  if (a->vocab <= kSampleWaveV) {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleRowsParams>), dim3(a->rows), dim3(64), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleRowsParams>), dim3(a->rows), dim3(64), 0, st, prm);
-  } else {
-    if (f32)
-      hipLaunchKernelGGL((sample_kernel<float, 4, SampleRowsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-    else
-      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleRowsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st,
-                         prm);
-  }
-  MTTS_LAUNCH_CHECK("sample_tokens_rows");
-  if (a->advance || a->unfinished) {
-    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos, a->finished,
-                       a->rows, a->unfinished, a->advance, a->pos_rows);
-    MTTS_LAUNCH_CHECK("sample_tokens_rows (advance)");
-  }
-  return MTTS_OK;
+  const char* const name = "sample_tokens_rows";
+  if (const int s = check_sample_rows_args(a, name)) return s;
+  MTTS_CHECK(!a->advance || a->step, "%s: advance needs step", name);
+  MTTS_CHECK(a->pos_rows >= 0, "%s: pos_rows=%d must be >= 0", name, a->pos_rows);
+  return launch_sample<SampleRowsParams>(a, name, (hipStream_t)stream);
 }
 
 extern "C" int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream) {
-  MTTS_CHECK(a && a->logits && a->tokens, "sample_tokens_slots: null pointer");
-  MTTS_CHECK(a->temperature && a->top_k && a->top_p && a->seed && a->draw,
-             "sample_tokens_slots: temperature, top_k, top_p, seed and draw are required");
-  MTTS_CHECK(a->dtype == MTTS_F32 || a->dtype == MTTS_BF16, "sample_tokens_slots: dtype must be f32 or bf16");
-  MTTS_CHECK(a->rows >= 1 && a->vocab >= 1 && a->vocab <= (1 << 24),
-             "sample_tokens_slots: rows=%d vocab=%d out of range", a->rows, a->vocab);
-  MTTS_CHECK(a->ld >= a->vocab && a->bias_ld >= 0 && (a->bias_ld == 0 || a->bias_ld >= a->vocab),
-             "sample_tokens_slots: row stride below vocab");
-  MTTS_CHECK(a->window >= 0 && a->window <= MTTS_SAMPLE_WINDOW_MAX, "sample_tokens_slots: window=%d outside [0, %d]",
-             a->window, MTTS_SAMPLE_WINDOW_MAX);
-  MTTS_CHECK(a->window == 0 || a->history, "sample_tokens_slots: window=%d needs history", a->window);
-  MTTS_CHECK(!a->max_length || (a->finished && a->length), "sample_tokens_slots: max_length needs finished and length");
-  MTTS_CHECK(a->pad_id >= 0 && a->pad_id < a->vocab && a->eos_id < a->vocab,
-             "sample_tokens_slots: pad_id=%d / eos_id=%d outside the vocabulary", a->pad_id, a->eos_id);
-  MTTS_CHECK(!a->history || (a->hist_cols >= 0 && a->hist_ld >= a->hist_cols),
-             "sample_tokens_slots: bad history shape");
-  MTTS_CHECK(!a->unfinished || a->finished, "sample_tokens_slots: unfinished needs finished");
+  const char* const name = "sample_tokens_slots";
+  if (const int s = check_sample_rows_args(a, name)) return s;
   MTTS_CHECK(!(a->advance && a->pos) || a->pos_rows == 0 || a->pos_rows == a->rows,
-             "sample_tokens_slots: pos_rows=%d must be 0 or rows=%d", a->pos_rows, a->rows);
-  hipStream_t st = (hipStream_t)stream;
-  SampleSlotsParams prm;
-  prm.a = *a;
-  const bool f32 = a->dtype == MTTS_F32;
-  if (a->vocab <= kSampleWaveV) {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, SampleSlotsParams>), dim3(a->rows), dim3(64), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, SampleSlotsParams>), dim3(a->rows), dim3(64), 0, st, prm);
-  } else {
-    if (f32)
-      hipLaunchKernelGGL((sample_kernel<float, 4, SampleSlotsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-    else
-      hipLaunchKernelGGL((sample_kernel<bf16_t, 4, SampleSlotsParams>), dim3(a->rows), dim3(kSampleThreads), 0, st,
-                         prm);
-  }
-  MTTS_LAUNCH_CHECK("sample_tokens_slots");
-  if (a->advance || a->unfinished) {
-    hipLaunchKernelGGL(sample_advance_slots_kernel, dim3(1), dim3(kSampleThreads), 0, st, a->step, a->pos,
-                       a->finished, a->rows, a->unfinished, a->advance, a->pos_rows);
-    MTTS_LAUNCH_CHECK("sample_tokens_slots (advance)");
-  }
-  return MTTS_OK;
+             "%s: pos_rows=%d must be 0 or rows=%d", name, a->pos_rows, a->rows);
+  return launch_sample<SampleSlotsParams>(a, name, (hipStream_t)stream);
 }

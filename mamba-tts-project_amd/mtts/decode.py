@@ -101,6 +101,100 @@ def _per_row(name, v, B, integer):
         raise ValueError(f"generate: {name} must hold {'integers' if integer else 'numbers'}") from None
 
 
+def _check_window(who, window):
+    if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window <= 256:
+        raise ValueError(f"{who}: repetition_window must be an integer in [0, 256]")
+
+
+def _check_vocab_ids(who, V, pad_id, eos_id):
+    if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
+        raise ValueError(f"{who}: pad_id / eos_id outside the vocabulary of {V}")
+
+
+def _check_request(m, B, n_new, prompt_tokens, start_token, logit_bias, pad_id, eos_id, prompt_lengths=None):
+    """What generate() and a session's admit() verify of a request of B rows
+    and n_new new tokens (the largest row's): the prompt's shape, its
+    positions against pos_embed, pad_id / eos_id, the logit_bias shape and the
+    start / prompt token ids.  Nothing is written.  Returns the prompt, its
+    length Tp and `lens`: with prompt_lengths (B,) of different values the
+    prompt cut at the longest row, its padding slots set to a valid id on a
+    copy, and the lengths as (B,) int32 on the model's device; else None."""
+    V = m.head.weight.shape[0]
+    if prompt_tokens is not None and (prompt_tokens.dim() != 2 or prompt_tokens.shape[0] != B
+                                      or prompt_tokens.shape[1] < 1):
+        raise ValueError(f"generate: prompt_tokens must be (B, Tp) with Tp >= 1 (B = {B})")
+    Tp = 1 if prompt_tokens is None else prompt_tokens.shape[1]
+    lens = None
+    if prompt_lengths is not None:
+        if prompt_tokens is None:
+            raise ValueError("generate: prompt_lengths needs prompt_tokens")
+        pl = torch.as_tensor(prompt_lengths)
+        if tuple(pl.shape) != (B,) or pl.dtype.is_floating_point or pl.dtype == torch.bool:
+            raise ValueError(f"generate: prompt_lengths must be ({B},) integers")
+        lo, hi = int(pl.min()), int(pl.max())
+        if lo < 1 or hi > Tp:
+            raise ValueError(f"generate: prompt_lengths must lie in [1, Tp = {Tp}] (got {lo}..{hi})")
+        # columns past the longest row are padding in every row; equal lengths are a rectangular prompt
+        prompt_tokens, Tp = prompt_tokens[:, :hi], hi
+        if lo < hi:
+            dev = m.token_embed.weight.device
+            lens = pl.to(device=dev, dtype=torch.int32)
+            # the padding slots' values are ignored: a valid id on a copy, before any check or embedding
+            keep = torch.arange(Tp, device=dev)[None, :] < lens[:, None]
+            prompt_tokens = torch.where(keep, prompt_tokens.to(dev), torch.zeros((), dtype=prompt_tokens.dtype,
+                                                                                  device=dev))
+    if Tp + n_new - 1 > m.pos_embed.num_embeddings:
+        raise IndexError(f"generate: {Tp} prompt + {n_new} new tokens need positions beyond pos_embed "
+                         f"({m.pos_embed.num_embeddings}) (index out of range in self)")
+    _check_vocab_ids("generate", V, pad_id, eos_id)
+    if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (B, V)):
+        raise ValueError(f"generate: logit_bias must be (V,) or (B, V) (B = {B})")
+    n_tok = m.token_embed.num_embeddings
+    if prompt_tokens is None:
+        if not 0 <= int(start_token) < n_tok:
+            raise IndexError("generate: start_token out of range of token_embed (index out of range in self)")
+    elif int(prompt_tokens.min()) < 0 or int(prompt_tokens.max()) >= n_tok:
+        raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
+    return prompt_tokens, Tp, lens
+
+
+def sampler_buffers(B, V, cap, dev):
+    """The per-row sampler's controls and history for B rows of at most `cap`
+    tokens, as device buffers a captured launch reads at run time: generate()'s
+    and a decode session's."""
+    return dict(temperature=torch.zeros(B, dtype=torch.float32, device=dev),
+                top_k=torch.zeros(B, dtype=torch.int32, device=dev),
+                top_p=torch.ones(B, dtype=torch.float32, device=dev),
+                row_seed=torch.zeros(B, dtype=torch.int64, device=dev),
+                draw=torch.zeros(B, dtype=torch.int32, device=dev),
+                penalty=torch.ones(B, dtype=torch.float32, device=dev),
+                max_length=torch.full((B,), cap, dtype=torch.int64, device=dev),
+                hist=torch.zeros(B, cap, dtype=torch.int64, device=dev),
+                unfinished=torch.zeros(1, dtype=torch.int32, device=dev),
+                bias=torch.zeros(B, V, dtype=torch.float32, device=dev))
+
+
+def capture_graph(body, restore):
+    """`body` as a hipGraph: two warm-up runs on a side stream (allocator,
+    library handles, lazily made workspaces), `restore()` before each of them,
+    before the capture and after it, so the buffers `body` advances are left
+    as `restore` makes them.  Returns the graph and what the captured `body`
+    returned (its static output)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            restore()
+            body()
+    torch.cuda.current_stream().wait_stream(s)
+    restore()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = body()
+    restore()
+    return g, out
+
+
 def _proj_blas(x, w, b=None, act=None):
     y = x @ w.t() if b is None else torch.addmm(b, x, w.t())
     return F.gelu(y) if act == "gelu" else y
@@ -485,25 +579,33 @@ class DecodeEngine:
             self.ctx_key = key
             self.ctx_refs = conds                  # strong references (see _same_ctx)
             self.ctx_versions = tuple(None if t is None else t._version for t in conds)
-            self.fused = self._fused_ok(cd, B)
-            if self.fused and self.OPTIONS["packed"]:
-                self._pack_ctx()
-            self.xpk = self.fused and self._xpk_ok()
-            self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(B)
+            self._latch_routing(B)
             self.graph = None
             self.gen_graphs = {}
             self.gen = None
             self.states = None
         if self.states is None:
-            self.states = []
-            for l in m.layers:
-                mm = l.mamba
-                self.states.append((torch.zeros(B, mm.d_inner, mm.d_conv, device=dev),
-                                    torch.zeros(B, mm.d_inner, mm.d_state, device=dev)))
-            self.tok_buf = torch.zeros(B, 1, dtype=torch.long, device=dev)
-            # per-row positions: int64 for the eager step's F.embedding, int32 for the fused step
-            self.pos_buf = torch.zeros(B, dtype=torch.long, device=dev)
-            self.pos32 = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._alloc_state(B, dev)
+
+    def _latch_routing(self, B):
+        """Which step runs over self.ctx at B rows, decided once per context:
+        the fused-epilogue step, its packed weights, the packed activations
+        (which also makes the head-major K / V and the packed FiLM images from
+        the context's rows) and the q projection inside the attention kernel."""
+        self.fused = self._fused_ok(self.ctx["cd"], B)
+        if self.fused and self.OPTIONS["packed"]:
+            self._pack_ctx()
+        self.xpk = self.fused and self._xpk_ok()
+        self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(B)
+
+    def _alloc_state(self, B, dev):
+        """The static per-layer (conv, SSM) states and token / position buffers of B rows, zeroed."""
+        self.states = [(torch.zeros(B, l.mamba.d_inner, l.mamba.d_conv, device=dev),
+                        torch.zeros(B, l.mamba.d_inner, l.mamba.d_state, device=dev)) for l in self.m.layers]
+        self.tok_buf = torch.zeros(B, 1, dtype=torch.long, device=dev)
+        # per-row positions: int64 for the eager step's F.embedding, int32 for the fused step
+        self.pos_buf = torch.zeros(B, dtype=torch.long, device=dev)
+        self.pos32 = torch.zeros(B, dtype=torch.int32, device=dev)
 
     # -- public ----------------------------------------------------------------
     @torch.no_grad()
@@ -543,22 +645,13 @@ class DecodeEngine:
             return logits, list(self.states)
         if self.graph is None:
             saved = [(a.clone(), b.clone()) for a, b in self.states]
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):  # warm up (allocator, library handles)
-                    step(self.tok_buf, self.pos_buf, self.states)
-            torch.cuda.current_stream().wait_stream(s)
-            for (a, b), (sa, sb) in zip(self.states, saved):
-                a.copy_(sa)
-                b.copy_(sb)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.out_buf = step(self.tok_buf, self.pos_buf, self.states)
-            for (a, b), (sa, sb) in zip(self.states, saved):  # capture ran the step once
-                a.copy_(sa)
-                b.copy_(sb)
-            self.graph = g
+
+            def restore():   # the warm-up runs advanced the states
+                for (a, b), (sa, sb) in zip(self.states, saved):
+                    a.copy_(sa)
+                    b.copy_(sb)
+
+            self.graph, self.out_buf = capture_graph(lambda: step(self.tok_buf, self.pos_buf, self.states), restore)
         self.graph.replay()
         if self.fused:
             self._post_token_flag(dev)
@@ -573,19 +666,10 @@ class DecodeEngine:
         if self.gen is None:
             cap = self.m.pos_embed.num_embeddings
             self.gen = dict(
-                temperature=torch.zeros(B, dtype=torch.float32, device=dev),
-                top_k=torch.zeros(B, dtype=torch.int32, device=dev),
-                top_p=torch.ones(B, dtype=torch.float32, device=dev),
-                row_seed=torch.zeros(B, dtype=torch.int64, device=dev),
-                draw=torch.zeros(B, dtype=torch.int32, device=dev),
-                penalty=torch.ones(B, dtype=torch.float32, device=dev),
-                max_length=torch.full((B,), cap, dtype=torch.int64, device=dev),
+                sampler_buffers(B, V, cap, dev),
                 seed=torch.zeros(1, dtype=torch.int64, device=dev), step=torch.zeros(1, dtype=torch.int32, device=dev),
-                hist=torch.zeros(B, cap, dtype=torch.int64, device=dev),
                 finished=torch.zeros(B, dtype=torch.int32, device=dev),
                 length=torch.zeros(B, dtype=torch.int64, device=dev),
-                unfinished=torch.zeros(1, dtype=torch.int32, device=dev),
-                bias=torch.zeros(B, V, dtype=torch.float32, device=dev),
                 host=torch.zeros(cap, dtype=torch.int32, pin_memory=True))
         return self.gen
 
@@ -613,8 +697,7 @@ class DecodeEngine:
             raise ValueError("generate: repetition_penalty must be finite and > 0 in every row")
         if not bool((caps >= 1).all()):
             raise ValueError("generate: max_new_tokens must be >= 1 in every row")
-        if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window <= 256:
-            raise ValueError("generate: repetition_window must be an integer in [0, 256]")
+        _check_window("generate", window)
         return dict(temperature=T.float(), top_k=k.int(), top_p=p.float(), row_seed=s, penalty=th.float(),
                     max_length=caps, window=window)
 
@@ -711,46 +794,13 @@ class DecodeEngine:
             n_new = int(max_new_tokens)
         if n_new < 1 or int(check_every) < 1:
             raise ValueError("generate: max_new_tokens and check_every must be >= 1")
-        if prompt_tokens is not None and (prompt_tokens.dim() != 2 or prompt_tokens.shape[0] != B
-                                          or prompt_tokens.shape[1] < 1):
-            raise ValueError("generate: prompt_tokens must be (B, Tp) with Tp >= 1")
-        Tp = 1 if prompt_tokens is None else prompt_tokens.shape[1]
-        lens = None
-        if prompt_lengths is not None:
-            if prompt_tokens is None:
-                raise ValueError("generate: prompt_lengths needs prompt_tokens")
-            pl = torch.as_tensor(prompt_lengths)
-            if tuple(pl.shape) != (B,) or pl.dtype.is_floating_point or pl.dtype == torch.bool:
-                raise ValueError(f"generate: prompt_lengths must be ({B},) integers")
-            lo, hi = int(pl.min()), int(pl.max())
-            if lo < 1 or hi > Tp:
-                raise ValueError(f"generate: prompt_lengths must lie in [1, Tp = {Tp}] (got {lo}..{hi})")
-            # columns past the longest row are padding in every row; equal lengths are a rectangular prompt
-            prompt_tokens, Tp = prompt_tokens[:, :hi], hi
-            if lo < hi:
-                lens = pl.to(device=dev, dtype=torch.int32)
-                # the padding slots' values are ignored: a valid id on a copy, before any check or embedding
-                keep = torch.arange(Tp, device=dev)[None, :] < lens[:, None]
-                prompt_tokens = torch.where(keep, prompt_tokens.to(dev), torch.zeros((), dtype=prompt_tokens.dtype,
-                                                                                      device=dev))
-        if Tp + n_new - 1 > m.pos_embed.num_embeddings:
-            raise IndexError(f"generate: {Tp} prompt + {n_new} new tokens need positions beyond pos_embed "
-                             f"({m.pos_embed.num_embeddings}) (index out of range in self)")
-        if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
-            raise ValueError(f"generate: pad_id / eos_id outside the vocabulary of {V}")
         if not per_row:
             if not 0 < top_p <= 1:
                 raise ValueError("generate: top_p must be in (0, 1]")
             if temperature < 0 or top_k < 0:
                 raise ValueError("generate: temperature and top_k must be >= 0")
-        if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (B, V)):
-            raise ValueError("generate: logit_bias must be (V,) or (B, V)")
-        n_tok = m.token_embed.num_embeddings
-        if prompt_tokens is None:
-            if not 0 <= int(start_token) < n_tok:
-                raise IndexError("generate: start_token out of range of token_embed (index out of range in self)")
-        elif int(prompt_tokens.min()) < 0 or int(prompt_tokens.max()) >= n_tok:
-            raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
+        prompt_tokens, Tp, lens = _check_request(m, B, n_new, prompt_tokens, start_token, logit_bias, pad_id, eos_id,
+                                                 prompt_lengths)
         self.check_errors()                         # a flag left by earlier decode_steps is theirs
         conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
         self._prepare(conds, (B, 1), dev)
@@ -789,18 +839,7 @@ class DecodeEngine:
             gr = self.gen_graphs.get(key)
             if gr is None:
                 g["bias"].zero_()
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    for _ in range(2):  # warm up (allocator, library handles, lazily made workspaces)
-                        rewind()
-                        body()
-                torch.cuda.current_stream().wait_stream(s)
-                rewind()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr):
-                    body()
-                self.gen_graphs[key] = gr
+                gr = self.gen_graphs[key] = capture_graph(body, rewind)[0]
             run = gr.replay
         # this call's state
         rewind()

@@ -962,6 +962,41 @@ def row_seeds(seed, rows):
     return out
 
 
+def _sample_rows(fn, logits, controls, window, io, one_row_pos=False):
+    """What the per-row and the slot form share (`fn` names the caller in
+    every message and, behind mtts_, the symbol called): _sample_io on `io`,
+    its keyword arguments; the seven per-row arrays `controls` (temperature,
+    top_k, top_p, seed, draw, penalty, max_length) checked and filled in; the
+    window and max_length rules; the call.  one_row_pos, the slot form's: a
+    `pos` of one row is a per-row position too, gated by its finished flag."""
+    a = L.SampleRowsArgs()
+    out, _step_t = _sample_io(a, fn, logits, **io)
+    rows, dev = logits.shape[0], logits.device
+    if one_row_pos and io["pos"] is not None and io["pos"].numel() == rows:
+        a.pos_rows = rows
+    per_row = (("temperature", torch.float32, True), ("top_k", torch.int32, True), ("top_p", torch.float32, True),
+               ("seed", torch.int64, True), ("draw", torch.int32, True), ("penalty", torch.float32, False),
+               ("max_length", torch.int64, False))
+    for (name, dt, required), t in zip(per_row, controls):
+        if t is None and not required:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (rows,)
+                or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a contiguous ({rows},) {dt} tensor on {dev}")
+        setattr(a, name, t.data_ptr())
+    window = int(window)
+    if not 0 <= window <= 256:
+        raise ValueError(f"{fn}: window must lie in [0, 256]")
+    if window > 0 and io["history"] is None:
+        raise ValueError(f"{fn}: window > 0 needs history")
+    max_length = controls[-1]
+    if max_length is not None and (io["finished"] is None or io["length"] is None):
+        raise ValueError(f"{fn}: max_length needs finished and length")
+    a.window = window
+    L.call("mtts_" + fn, a)
+    return out
+
+
 def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
                        logit_bias=None, step, advance=False, out=None, history=None, step0=0, eos_id=None, pad_id=0,
                        finished=None, length=None, unfinished=None, pos=None):
@@ -981,32 +1016,10 @@ def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty
     the row's last min(window, draw[r], step - step0) history columns (ids
     outside [0, V) are skipped); it needs `history`.
     Everything else is as in sample_tokens.  No device value is read here."""
-    fn = "sample_tokens_rows"
-    a = L.SampleRowsArgs()
-    out, _step_t = _sample_io(a, fn, logits, logit_bias, step, advance, out, history, step0, eos_id, pad_id,
-                              finished, length, unfinished, pos)
-    rows, dev = logits.shape[0], logits.device
-    per_row = (("temperature", temperature, torch.float32, True), ("top_k", top_k, torch.int32, True),
-               ("top_p", top_p, torch.float32, True), ("seed", seed, torch.int64, True),
-               ("draw", draw, torch.int32, True), ("penalty", penalty, torch.float32, False),
-               ("max_length", max_length, torch.int64, False))
-    for name, t, dt, required in per_row:
-        if t is None and not required:
-            continue
-        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (rows,)
-                or not t.is_contiguous()):
-            raise ValueError(f"{fn}: {name} must be a contiguous ({rows},) {dt} tensor on {dev}")
-        setattr(a, name, t.data_ptr())
-    window = int(window)
-    if not 0 <= window <= 256:
-        raise ValueError(f"{fn}: window must lie in [0, 256]")
-    if window > 0 and history is None:
-        raise ValueError(f"{fn}: window > 0 needs history")
-    if max_length is not None and (finished is None or length is None):
-        raise ValueError(f"{fn}: max_length needs finished and length")
-    a.window = window
-    L.call("mtts_sample_tokens_rows", a)
-    return out
+    return _sample_rows("sample_tokens_rows", logits, (temperature, top_k, top_p, seed, draw, penalty, max_length), window,
+                        dict(logit_bias=logit_bias, step=step, advance=advance, out=out, history=history, step0=step0,
+                             eos_id=eos_id, pad_id=pad_id, finished=finished, length=length, unfinished=unfinished,
+                             pos=pos))
 
 
 def sample_tokens_slots(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
@@ -1022,33 +1035,9 @@ def sample_tokens_slots(logits, *, temperature, top_k, top_p, seed, draw, penalt
     a row finished at entry gets pad_id in `out` and keeps its history, draw
     and length; and advance=True with per-row `pos` moves only the rows that
     are unfinished after the draw.  No device value is read here."""
-    fn = "sample_tokens_slots"
-    a = L.SampleRowsArgs()
     if step is not None and not isinstance(step, torch.Tensor):
-        raise ValueError(f"{fn}: step must be None or a one-element int32 device tensor")
-    out, _step_t = _sample_io(a, fn, logits, logit_bias, step, advance, out, history, 0, eos_id, pad_id, finished,
-                              length, unfinished, pos)
-    rows, dev = logits.shape[0], logits.device
-    if pos is not None and pos.numel() == rows:
-        a.pos_rows = rows                       # one row is a per-row position too: gated by its finished flag
-    per_row = (("temperature", temperature, torch.float32, True), ("top_k", top_k, torch.int32, True),
-               ("top_p", top_p, torch.float32, True), ("seed", seed, torch.int64, True),
-               ("draw", draw, torch.int32, True), ("penalty", penalty, torch.float32, False),
-               ("max_length", max_length, torch.int64, False))
-    for name, t, dt, required in per_row:
-        if t is None and not required:
-            continue
-        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != (rows,)
-                or not t.is_contiguous()):
-            raise ValueError(f"{fn}: {name} must be a contiguous ({rows},) {dt} tensor on {dev}")
-        setattr(a, name, t.data_ptr())
-    window = int(window)
-    if not 0 <= window <= 256:
-        raise ValueError(f"{fn}: window must lie in [0, 256]")
-    if window > 0 and history is None:
-        raise ValueError(f"{fn}: window > 0 needs history")
-    if max_length is not None and (finished is None or length is None):
-        raise ValueError(f"{fn}: max_length needs finished and length")
-    a.window = window
-    L.call("mtts_sample_tokens_slots", a)
-    return out
+        raise ValueError("sample_tokens_slots: step must be None or a one-element int32 device tensor")
+    return _sample_rows("sample_tokens_slots", logits, (temperature, top_k, top_p, seed, draw, penalty, max_length),
+                        window, dict(logit_bias=logit_bias, step=step, advance=advance, out=out, history=history, step0=0,
+                                     eos_id=eos_id, pad_id=pad_id, finished=finished, length=length,
+                                     unfinished=unfinished, pos=pos), one_row_pos=True)

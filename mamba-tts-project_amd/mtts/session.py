@@ -26,7 +26,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .attn_kernels import key_counts
-from .decode import DecodeEngine, _is_scalar
+from .decode import (DecodeEngine, _check_request, _check_vocab_ids, _check_window, _is_scalar, capture_graph,
+                     sampler_buffers)
 from .linear import cast_weight
 
 
@@ -70,22 +71,19 @@ class DecodeSession:
         slots, max_keys = int(slots), int(max_keys)
         if slots < 1 or max_keys < 1:
             raise ValueError("open_session: slots and max_keys must be >= 1")
-        if not 0 <= int(pad_id) < V or (eos_id is not None and not 0 <= int(eos_id) < V):
-            raise ValueError(f"open_session: pad_id / eos_id outside the vocabulary of {V}")
-        w = repetition_window
-        if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 256:
-            raise ValueError("open_session: repetition_window must be an integer in [0, 256]")
+        _check_vocab_ids("open_session", V, pad_id, eos_id)
+        _check_window("open_session", repetition_window)
         dev = m.token_embed.weight.device
         if dev.type != "cuda":
             raise RuntimeError("open_session runs on the HIP kernels only (no CPU path)")
         self.slots, self.max_keys, self.V = slots, max_keys, V
-        self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), w
+        self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), repetition_window
         self.use_graph = bool(use_graph)
         self.dev = dev
         d = m.token_embed.weight.shape[1]
         cd = self.cd = m._cd()
         P = self.P = m.pos_embed.num_embeddings
-        # a private engine: the step functions and their predicates are the engine's, the buffers are ours
+        # a private engine over a context of `slots` idle rows, routed and given its buffers by its own methods
         eng = self.eng = DecodeEngine(m, use_graph=False)
         keep = torch.zeros(slots, max_keys, dtype=torch.bool, device=dev)
         keep[:, 0] = True                                   # a fully masked row would give NaN
@@ -100,49 +98,33 @@ class DecodeSession:
             ca = l.cross_attn
             p["Wkv"] = cast_weight(ca.in_proj_weight, cd)[d:]
             p["bkv"] = cast_weight(ca.in_proj_bias, cd)[d:]
-            for name in ("k", "v", "gamma", "beta"):        # idle rows are zero
+            for name in ("k", "v", "gamma", "beta"):        # idle rows are zero, before the latch below copies them
                 p[name].zero_()
         eng.ctx = ctx
-        eng.fused = eng._fused_ok(cd, slots)
-        if eng.fused and eng.OPTIONS["packed"]:
-            eng._pack_ctx()
-        eng.xpk = eng.fused and eng._xpk_ok()               # also makes khm / vhm and the packed FiLM images
-        eng.fuse_q = eng.xpk and eng.OPTIONS["fuse_q"] and eng._fuse_q_ok(slots)
-        eng.states = [(torch.zeros(slots, l.mamba.d_inner, l.mamba.d_conv, device=dev),
-                       torch.zeros(slots, l.mamba.d_inner, l.mamba.d_state, device=dev)) for l in m.layers]
-        eng.tok_buf = torch.full((slots, 1), self.pad, dtype=torch.long, device=dev)
-        eng.pos_buf = torch.zeros(slots, dtype=torch.long, device=dev)
-        eng.pos32 = torch.zeros(slots, dtype=torch.int32, device=dev)
+        eng._latch_routing(slots)                           # also makes khm / vhm and the packed FiLM images
+        eng._alloc_state(slots, dev)
+        eng.tok_buf.fill_(self.pad)
         # the batch-1 prefill runs on an engine of its own states; the context's constants are shared
         pre = self.pre = DecodeEngine(m, use_graph=False)
         pre.ctx = ctx
-        pre.states = [(torch.zeros(1, *cs.shape[1:], device=dev), torch.zeros(1, *ss.shape[1:], device=dev))
-                      for cs, ss in eng.states]
+        pre._alloc_state(1, dev)
         # length (int64) and finished (int32) share one allocation: a poll is one copy
         self._raw = torch.zeros(12 * slots, dtype=torch.uint8, device=dev)
         self._raw_host = torch.zeros(12 * slots, dtype=torch.uint8, pin_memory=True)
         self.length = self._raw[:8 * slots].view(torch.int64)
         self.finished = self._raw[8 * slots:].view(torch.int32)
         self.finished.fill_(1)
-        self.g = dict(
-            temperature=torch.zeros(slots, dtype=torch.float32, device=dev),
-            top_k=torch.zeros(slots, dtype=torch.int32, device=dev),
-            top_p=torch.ones(slots, dtype=torch.float32, device=dev),
-            row_seed=torch.zeros(slots, dtype=torch.int64, device=dev),
-            draw=torch.zeros(slots, dtype=torch.int32, device=dev),
-            penalty=torch.ones(slots, dtype=torch.float32, device=dev),
-            max_length=torch.full((slots,), P, dtype=torch.int64, device=dev),
-            hist=torch.zeros(slots, P, dtype=torch.int64, device=dev),
-            unfinished=torch.zeros(1, dtype=torch.int32, device=dev),
-            bias=torch.zeros(slots, V, dtype=torch.float32, device=dev))
+        self.g = sampler_buffers(slots, V, P, dev)
         self.logits = torch.zeros(slots, V, device=dev, dtype=cd)
         self.state = ["idle"] * slots                       # idle -> live (admit) -> done (poll) -> idle (take)
         self.lengths = [0] * slots
         self.graph = None
         self.captures = 0
         self.replays = 0
-        if self.use_graph:
-            self._capture()
+        if self.use_graph:                                  # once, with every slot idle
+            self.graph, self.logits = capture_graph(self._body, self._idle_all)
+            self.captures += 1
+            DecodeSession.CAPTURES += 1
 
     # -- the step ---------------------------------------------------------------
     def _sample(self, logits, rows):
@@ -182,25 +164,6 @@ class DecodeSession:
         self.finished.fill_(1)
         self.length.zero_()
         self.g["draw"].zero_()
-
-    def _capture(self):
-        """Once, at open, with every slot idle: warm up on a side stream, put
-        the buffers back, capture, put them back again (as generate does)."""
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._idle_all()
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        self._idle_all()
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr):
-            self.logits = self._body()
-        self._idle_all()
-        self.graph = gr
-        self.captures += 1
-        DecodeSession.CAPTURES += 1
 
     @torch.no_grad()
     def run(self, n=1):
@@ -263,24 +226,8 @@ class DecodeSession:
             raise ValueError(f"admit: {S} conditioning keys exceed the session's max_keys = {self.max_keys}")
         if S < 1:
             raise ValueError("admit: the conditioning sequence is empty")
-        pt = prompt_tokens
-        if pt is not None:
-            if pt.dim() == 1:
-                pt = pt[None]
-            if pt.dim() != 2 or pt.shape[0] != 1 or pt.shape[1] < 1:
-                raise ValueError("generate: prompt_tokens must be (Tp,) or (1, Tp) with Tp >= 1")
-        Tp = 1 if pt is None else pt.shape[1]
-        if Tp + cap - 1 > self.P:
-            raise IndexError(f"generate: {Tp} prompt + {cap} new tokens need positions beyond pos_embed "
-                             f"({self.P}) (index out of range in self)")
-        if logit_bias is not None and tuple(logit_bias.shape) not in ((V,), (1, V)):
-            raise ValueError("generate: logit_bias must be (V,) or (1, V)")
-        n_tok = m.token_embed.num_embeddings
-        if pt is None:
-            if not 0 <= int(start_token) < n_tok:
-                raise IndexError("generate: start_token out of range of token_embed (index out of range in self)")
-        elif int(pt.min()) < 0 or int(pt.max()) >= n_tok:
-            raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
+        pt = prompt_tokens[None] if prompt_tokens is not None and prompt_tokens.dim() == 1 else prompt_tokens
+        pt, Tp, _ = _check_request(m, 1, cap, pt, start_token, logit_bias, self.pad, self.eos)
         if self.state[slot] != "idle":
             raise RuntimeError(f"admit: slot {slot} holds a request that has not been taken")
         # -- conditioning: [ref ‖ text] padded to max_keys, projected, written in place

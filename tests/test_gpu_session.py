@@ -278,6 +278,54 @@ def test_admission_checks_come_first():
         ses.admit(2, **ok)                                  # finished and polled, but not taken
 
 
+def test_generate_and_admit_refuse_the_same_requests():
+    """Every bad request of test_admission_checks_come_first, plus positions
+    past pos_embed, an out-of-range start token and a wrong-shaped logit_bias:
+    generate() on the one-row batch and admit() raise the same exception type
+    naming the same argument, and the session is left as it was.  (Too many
+    keys is the one request generate() cannot refuse: max_keys is the
+    session's own limit, so that row holds admit() to its message alone.)"""
+    m = _model(max_len=64)
+    ses = m.open_session(SLOTS, KEYS, repetition_window=WINDOW)
+    ses.admit(0, **_request(0, 20))
+    ses.run(3)
+    saved, bufs = _snapshot(ses)
+    ok = _request(1, 10)
+    prompt = torch.zeros(10, dtype=torch.long, device=DEV)
+    bad = [  # (what changes in the request, exception, the argument both messages name)
+        (dict(text_hidden=torch.zeros(KEYS - 3, D, device=DEV), ref_hidden=torch.zeros(4, D, device=DEV)), ValueError,
+         None),                                             # too many keys: a session's limit, generate() has none
+        (dict(top_p=0.0), ValueError, "top_p"),
+        (dict(repetition_penalty=float("inf")), ValueError, "repetition_penalty"),
+        (dict(max_new_tokens=0), ValueError, "max_new_tokens"),
+        (dict(max_new_tokens=56, prompt_tokens=prompt), IndexError, "pos_embed"),       # 10 + 56 - 1 > 64
+        (dict(start_token=V), IndexError, "start_token"),
+        (dict(start_token=-1), IndexError, "start_token"),
+        (dict(logit_bias=torch.zeros(V + 1, device=DEV)), ValueError, "logit_bias"),
+        (dict(logit_bias=torch.zeros(2, V, device=DEV)), ValueError, "logit_bias"),
+    ]
+    for over, exc, arg in bad:
+        req = dict(ok, **over)
+        with pytest.raises(exc) as by_admit:
+            ses.admit(1, **req)
+        if arg is None:
+            assert "max_keys" in str(by_admit.value)
+            continue
+        text, z, mask = _padded(req)
+        one = {k: [req[k]] for k in ("temperature", "top_k", "top_p", "seed", "repetition_penalty")}
+        pt = req.get("prompt_tokens")
+        with pytest.raises(exc) as by_generate:
+            m.generate(text, z, [req["max_new_tokens"]], text_mask=mask, repetition_window=WINDOW,
+                       prompt_tokens=None if pt is None else pt[None], start_token=req.get("start_token", 0),
+                       logit_bias=req.get("logit_bias"), **one)
+        assert type(by_admit.value) is type(by_generate.value) is exc
+        assert arg in str(by_admit.value) and arg in str(by_generate.value), (by_admit.value, by_generate.value)
+    assert ses.captures == 1 and ses.state == ["live", "idle", "idle"]
+    for was, now in zip(saved, bufs):
+        assert torch.equal(was, now)                        # nothing was overwritten on the way to an error
+    assert m._engine is None or not m._engine.gen_graphs    # and generate() captured nothing
+
+
 def test_session_does_not_disturb_generate_or_decode_step():
     from test_gpu_generate import B, _conds
     m, fresh = _model(), _model()
