@@ -63,35 +63,46 @@ def _mask_u8(kpm, B, S):
     return kpm.view(torch.uint8)
 
 
+def _decode_args(who, q, k, v, n_heads, kpm, want_out, want_packed):
+    """The front end of the single-query calls: AttnFwdArgs for q (B, d)
+    against k / v (B, S, d) channel-last or HEAD-MAJOR (B, H, S, hd)
+    contiguous (one contiguous K and V block per (batch, head): kv_hs), the
+    mask as bytes, and the outputs asked for.  Returns (args, out (B, 1, d) or
+    None, PackedAct or None, keep); `keep` holds the aligned copies the
+    pointers in args may refer to and must live until the launch.  `who`
+    names the caller in the errors."""
+    from .ops import PackedAct
+    B, d = q.shape
+    q3 = q[:, None]
+    if not _aligned(q3):
+        q3 = q3.contiguous()
+    out = torch.empty(B, 1, d, device=q.device, dtype=q.dtype) if want_out else None
+    yp = PackedAct.empty(B, d, q.device) if want_packed else None
+    o3 = q3 if out is None else out                         # strides only: no row-major out
+    if k.dim() == 4:
+        H, S, hd = k.shape[1:]
+        if H != n_heads or H * hd != d or k.shape != v.shape or not (k.is_contiguous() and v.is_contiguous()):
+            raise ValueError(f"{who}: head-major k / v must be contiguous (B, H, S, hd)")
+        m = _mask_u8(kpm, B, S)
+        a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, o3, None)
+        a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
+    else:
+        k, v = _prep(k), _prep(v)
+        m = _mask_u8(kpm, B, k.shape[1])
+        a = _fwd_args(q3, k, v, n_heads, m, o3, None)
+    a.out = 0 if out is None else out.data_ptr()
+    a.out_packed = None if yp is None else yp.data.data_ptr()
+    return a, out, yp, (q3, k, v, m)
+
+
 def attention_decode_packed(q, k, v, n_heads, kpm=None):
     """Single-query attention (q (B, d), decode step) returning the output
     as the packed activation image of the output projection (ops.PackedAct;
     csrc/attn.hip single-pass decode kernel).  k / v: (B, S, d) channel-last,
     or HEAD-MAJOR (B, H, S, hd) contiguous (the decode engine's per-context
     copies): one contiguous K and V block per (batch, head)."""
-    from .ops import PackedAct
-    B, d = q.shape
-    q3 = q[:, None]
-    if not _aligned(q3):
-        q3 = q3.contiguous()
-    if k.dim() == 4:   # head-major
-        H, S, hd = k.shape[1:]
-        if H != n_heads or H * hd != d or not (k.is_contiguous() and v.is_contiguous()):
-            raise ValueError("attention_decode_packed: head-major k / v must be contiguous (B, H, S, hd)")
-        m = _mask_u8(kpm, B, S)
-        out = torch.empty(B, 1, d, device=q.device, dtype=q.dtype)
-        yp = PackedAct.empty(B, d, q.device)
-        a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, out, None)
-        a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
-        a.out_packed = yp.data.data_ptr()
-        L.call("mtts_attention_fwd", a)
-        return yp
-    k, v = _prep(k), _prep(v)
-    m = _mask_u8(kpm, B, k.shape[1])
-    out = torch.empty(B, 1, d, device=q.device, dtype=q.dtype)
-    yp = PackedAct.empty(B, d, q.device)
-    a = _fwd_args(q3, k, v, n_heads, m, out, None)
-    a.out_packed = yp.data.data_ptr()
+    # the row-major out is allocated and stored as well (as it always was: the captured graphs hold that store)
+    a, out, yp, keep = _decode_args("attention_decode_packed", q, k, v, n_heads, kpm, want_out=True, want_packed=True)
     L.call("mtts_attention_fwd", a)
     return yp
 
@@ -103,21 +114,15 @@ def attention_decode_qproj_packed(x, wq, bq, ln_w, ln_b, eps, k, v, n_heads, kpm
     as the packed projections' LayerNorm prologue computes it; k / v
     head-major (B, H, S, hd) contiguous.  Returns the output as the packed
     activation image of the output projection (ops.PackedAct)."""
-    from .ops import PackedAct
     B, d = x.shape
     if k.dim() != 4 or not (k.is_contiguous() and v.is_contiguous()):
         raise ValueError("attention_decode_qproj_packed: head-major contiguous (B, H, S, hd) k / v")
     if x.dtype != torch.bfloat16 or x.stride(1) != 1 or wq.dtype != torch.bfloat16 or wq.stride(1) != 1 \
             or wq.stride(0) != d:
         raise ValueError("attention_decode_qproj_packed: bf16 x (B, d) and row-major bf16 wq (d, d)")
-    H, S, hd = k.shape[1:]
-    m = _mask_u8(kpm, B, S)
-    yp = PackedAct.empty(B, d, x.device)
-    q3 = x[:, None]
-    a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, q3, None)   # no row-major out
-    a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
-    a.out = 0
-    a.out_packed = yp.data.data_ptr()
+    # x stands in for q (the kernel computes q; the C side checks x itself): no row-major out
+    a, _, yp, keep = _decode_args("attention_decode_qproj_packed", x, k, v, n_heads, kpm, want_out=False,
+                                  want_packed=True)
     qa = L.AttnQProjArgs()
     qa.f = a
     qa.x, qa.x_rs = x.data_ptr(), x.stride(0)
@@ -169,7 +174,6 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     want_lse also the (B, H) fp32 log-sum-exp.  workspace: a uint8 device
     tensor of decode_split_workspace(B, H, hd, S) bytes to keep the partials
     in (the decode engine holds one per context); None allocates one."""
-    from .ops import PackedAct
     for t in (q, k, v):
         if not t.is_cuda:
             raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
@@ -181,30 +185,13 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     if not (q.dtype == k.dtype == v.dtype):
         raise TypeError("q, k, v must share a dtype")
     hd = d // n_heads
-    q3 = q[:, None]
-    if not _aligned(q3):
-        q3 = q3.contiguous()
-    out = None if packed else torch.empty(B, 1, d, device=q.device, dtype=q.dtype)
-    yp = PackedAct.empty(B, d, q.device) if packed else None
-    o3 = q3 if out is None else out                         # strides only: no row-major out when packed
-    if k.dim() == 4:   # head-major
-        H, S, hdk = k.shape[1:]
-        if H != n_heads or hdk != hd or k.shape != v.shape or not (k.is_contiguous() and v.is_contiguous()):
-            raise ValueError("attention_decode_split: head-major k / v must be contiguous (B, H, S, hd)")
-        m = _mask_u8(kpm, B, S)
-        a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, o3, None)
-        a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
-    else:
-        k, v = _prep(k), _prep(v)
-        S = k.shape[1]
-        m = _mask_u8(kpm, B, S)
-        a = _fwd_args(q3, k, v, n_heads, m, o3, None)
+    a, out, yp, keep = _decode_args("attention_decode_split", q, k, v, n_heads, kpm, want_out=not packed,
+                                    want_packed=packed)
+    S = a.kv_len
     if S < 1:
         raise ValueError("attention_decode_split: the key side is empty")
     lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
     a.lse = L.ptr(lse)
-    a.out = 0 if out is None else out.data_ptr()
-    a.out_packed = None if yp is None else yp.data.data_ptr()
     if kv_lens is not None:
         if kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,) or not kv_lens.is_cuda \
                 or not kv_lens.is_contiguous():

@@ -1712,8 +1712,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(MttsAttnFwdArgs a) {
   }
 }
 
-// Short key sides (kv_len <= U * 256 / (HD / 8); C4's 128 text keys): every
-// key of the (batch, head) in registers at once, so the softmax needs no
+// Short key sides (kv_len <= U * 256 / (HD / 8); C4's 128 text keys) and each
+// chunk of a long one (decode_single_pass below, the one body of
+// attn_decode1_kernel and attn_decode_split_kernel): every key of the
+// (batch, head) or chunk in registers at once, so the softmax needs no
 // online rescaling: scores -> block max (wave shuffles + 4 LDS words) ->
 // p = exp2(s - max) -> P.V and sum(p) reduced over the wave's groups by
 // shuffles and over the 4 waves through LDS (fixed order).  All loads are
@@ -1819,137 +1821,29 @@ __device__ __forceinline__ void qproj_head(const QProj& qp, int b, int hh, float
   block_sync();
 }
 
-template <typename T, int HD, int U, bool QP = false>
-__global__ __launch_bounds__(256) void attn_decode1_kernel(MttsAttnFwdArgs a, QProj qp) {
+// Keys one workgroup of the single-pass body holds in registers: u per key
+// group, 256 / (HD / 8) groups.  The largest U instantiated bounds what the
+// single-pass kernels take and is the split-key kernel's chunk.
+constexpr int kDecodeU = 8;
+constexpr int single_pass_keys(int hd, int u = kDecodeU) { return u * (256 / (hd / 8)); }
+constexpr int split_chunk(int hd) { return single_pass_keys(hd); }
+
+// The single pass over keys k0 + g + u * NG, u < U, of row (b, hh), n the
+// row's key count (an index at or past n loads key k0 and counts for nothing);
+// q holds the thread's 8 query values.  Every thread
+// gets the block max M (log2 units, -inf when every key is masked); threads
+// < HD also the sum of p and their dimension's unnormalised accumulator.
+// attn_decode1_kernel and attn_decode_split_kernel both run exactly this, so
+// a row's bits do not depend on which of them, or which chunk, holds its keys.
+template <typename T, int HD, int U>
+__device__ __forceinline__ void decode_single_pass(const MttsAttnFwdArgs& a, int b, int hh, const float (&q)[8], int k0,
+                                                   int n, float& M, float& L, float& o) {
   constexpr int G = HD / 8, NG = 256 / G;
+  static_assert(U <= kDecodeU, "single_pass_keys bounds the key range by kDecodeU");
   __shared__ float swm[4], swl[4], sacc[4][HD];
-  __shared__ float sx[QP ? kQpMaxDm : 1], sq[QP ? HD : 1], sred[4];
-  const int bh = blockIdx.x, b = bh / a.heads, hh = bh % a.heads;
   const int g = threadIdx.x / G, gl = threadIdx.x % G, d0 = gl * 8, wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const float c = a.scale * kLog2e;
-  float q[8];
-  if constexpr (QP) {
-    qproj_head<HD>(qp, b, hh, sx, sq, sred);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = sq[d0 + e];
-  } else {
-    ld8((const T*)a.q + b * a.q_bs + hh * HD + d0, q);
-  }
-  const int64_t hs = a.kv_hs ? a.kv_hs : HD;
-  const T* kb = (const T*)a.k + b * a.k_bs + hh * hs + d0;
-  const T* vb = (const T*)a.v + b * a.v_bs + hh * hs + d0;
-  const uint8_t* mb = a.key_padding_mask ? a.key_padding_mask + b * a.mask_bs : (const uint8_t*)a.q;
-  const uint32_t mmask = a.key_padding_mask ? 0xffu : 0u;
-  float kx[U][8], vx[U][8];
-  bool ok[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int j = g + u * NG;
-    const int jj = j < a.kv_len ? j : 0;
-    ld8(kb + (int64_t)jj * a.k_ls, kx[u]);
-    ld8(vb + (int64_t)jj * a.v_ls, vx[u]);
-    ok[u] = j < a.kv_len && ((uint32_t)mb[a.key_padding_mask ? jj : 0] & mmask) == 0;
-  }
-  float sc[U], m = -INFINITY;
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    float sv = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sv = fmaf(q[e], kx[u][e], sv);
-    sv = group_sum<G>(sv, lane);
-    sc[u] = ok[u] ? sv * c : -INFINITY;
-    m = fmaxf(m, sc[u]);
-  }
-  m = groups_max<G>(m, lane);
-  if ((threadIdx.x & 63) == 0) swm[wave] = m;
-  block_sync();
-  const float M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
-  float l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const float p = ok[u] ? exp2f(sc[u] - M) : 0.f;
-    l += p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vx[u][e], acc[e]);
-  }
-  l = groups_sum<G>(l, lane);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = groups_sum<G>(acc[e], lane);
-  if ((threadIdx.x & 63) < G) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sacc[wave][d0 + e] = acc[e];
-    if (gl == 0) swl[wave] = l;
-  }
-  block_sync();
-  if (threadIdx.x < HD) {
-    const float L = (swl[0] + swl[1]) + (swl[2] + swl[3]);
-    const float o = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
-    // fully masked: L = 0 -> 0/0 = NaN (torch MHA), lse = -inf
-    if (a.out) mtts::stf((T*)a.out + b * a.o_bs + hh * HD + threadIdx.x, o / L);
-    if constexpr (sizeof(T) == 2) {   // packed activation image for the output projection
-      if (a.out_packed) ((mtts::bf16_t*)a.out_packed)[mtts::xpk_index(b, hh * HD + threadIdx.x)] = mtts::f2bf(o / L);
-    }
-    if (a.lse && threadIdx.x == 0) a.lse[(int64_t)b * a.heads + hh] = M == -INFINITY ? -INFINITY : (M + log2f(L)) * kLn2;
-  }
-}
-
-template <typename T, int HD>
-void launch_decode(const MttsAttnFwdArgs* a, hipStream_t st) {
-  constexpr int NG = 256 / (HD / 8);
-  const dim3 grid(a->batch * a->heads);
-  const QProj none{};
-  if (a->kv_len <= 4 * NG) hipLaunchKernelGGL((attn_decode1_kernel<T, HD, 4>), grid, dim3(256), 0, st, *a, none);
-  else if (a->kv_len <= 8 * NG) hipLaunchKernelGGL((attn_decode1_kernel<T, HD, 8>), grid, dim3(256), 0, st, *a, none);
-  else hipLaunchKernelGGL((attn_decode_kernel<T, HD>), grid, dim3(256), 0, st, *a);
-}
-
-template <int HD>
-void launch_decode_qp(const MttsAttnFwdArgs* a, const QProj& qp, hipStream_t st) {
-  constexpr int NG = 256 / (HD / 8);
-  const dim3 grid(a->batch * a->heads);
-  if (a->kv_len <= 4 * NG)
-    hipLaunchKernelGGL((attn_decode1_kernel<mtts::bf16_t, HD, 4, true>), grid, dim3(256), 0, st, *a, qp);
-  else
-    hipLaunchKernelGGL((attn_decode1_kernel<mtts::bf16_t, HD, 8, true>), grid, dim3(256), 0, st, *a, qp);
-}
-
-// ---------------------------------------------------------------------------
-// Long key sides (the 5248-key conditioning of train.py), split over the key
-// axis: workgroup (b, h, c) owns the CK = 16384 / HD keys of chunk c -- what
-// attn_decode1_kernel<T, HD, 8> holds in registers -- and runs that kernel's
-// single-pass body on them (all K and V of the chunk loaded before any
-// arithmetic, no online rescaling), leaving one fp32 partial (chunk max in
-// log2 units, sum p, HD unnormalised accumulators) in the workspace; the
-// merge launch sums a row's partials in chunk order.  CK depends on the head
-// dim alone, so a row's chunks, and with them every rounding of its result,
-// are the same at any batch size, row index and kv_len.  A row reads only its
-// own n_b = min(kv_lens[b], kv_len) keys: chunks at or past n_b return before
-// any load, key indices past n_b are clamped to the chunk's first key.
-// No atomics, no hand-off inside a launch.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int row_keys(const int32_t* kv_lens, int b, int kv_len) {
-  if (!kv_lens) return kv_len;
-  const int n = kv_lens[b];
-  return n < 0 ? 0 : (n < kv_len ? n : kv_len);
-}
-
-constexpr int split_chunk(int hd) { return 16384 / hd; }
-
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_decode_split_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens, float* ws,
-                                                                 int nchunk) {
-  constexpr int G = HD / 8, NG = 256 / G, U = 8, CK = NG * U;
-  static_assert(CK == split_chunk(HD), "a chunk is what the single-pass kernel holds in registers");
-  __shared__ float swm[4], swl[4], sacc[4][HD];
-  const int bh = blockIdx.x, chunk = blockIdx.y, b = bh / a.heads, hh = bh % a.heads;
-  const int n = row_keys(kv_lens, b, a.kv_len), k0 = chunk * CK;
-  if (k0 >= n) return;   // uniform over the workgroup; before any load or barrier
-  const int g = threadIdx.x / G, gl = threadIdx.x % G, d0 = gl * 8, wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const float c = a.scale * kLog2e;
-  float q[8];
-  ld8((const T*)a.q + b * a.q_bs + hh * HD + d0, q);
   const int64_t hs = a.kv_hs ? a.kv_hs : HD;
   const T* kb = (const T*)a.k + b * a.k_bs + hh * hs + d0;
   const T* vb = (const T*)a.v + b * a.v_bs + hh * hs + d0;
@@ -1976,9 +1870,11 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(MttsAttnFwdArgs 
     m = fmaxf(m, sc[u]);
   }
   m = groups_max<G>(m, lane);
-  if (lane == 0) swm[wave] = m;
+  // (the unsigned lane tests here and below: on the int `lane` the compiler keeps it in a register through the
+  // pass, which takes attn_decode1_kernel<bf16, 128, 4, QP> from 63 to 65 VGPRs and from 8 waves to 7)
+  if ((threadIdx.x & 63) == 0) swm[wave] = m;
   block_sync();
-  const float M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
+  M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
   float l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -1990,17 +1886,105 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(MttsAttnFwdArgs 
   l = groups_sum<G>(l, lane);
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = groups_sum<G>(acc[e], lane);
-  if (lane < G) {
+  if ((threadIdx.x & 63) < G) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) sacc[wave][d0 + e] = acc[e];
     if (gl == 0) swl[wave] = l;
   }
   block_sync();
   if (threadIdx.x < HD) {
-    // every key of the chunk masked: M = -inf, sum p = 0, accumulators 0
+    L = (swl[0] + swl[1]) + (swl[2] + swl[3]);
+    o = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
+  }
+}
+
+// Dimension t of row (b, hh) from the block max M, sum of p L and accumulator
+// o: row-major out if there is one, the packed activation image of the output
+// projection (bf16), lse by thread 0.  No key or every key masked: L = 0 ->
+// 0/0 = NaN (torch MHA), lse = -inf.
+template <typename T, int HD>
+__device__ __forceinline__ void decode_store_row(const MttsAttnFwdArgs& a, int b, int hh, int t, float M, float L,
+                                                 float o) {
+  if (a.out) mtts::stf((T*)a.out + b * a.o_bs + hh * HD + t, o / L);
+  if constexpr (sizeof(T) == 2) {
+    if (a.out_packed) ((mtts::bf16_t*)a.out_packed)[mtts::xpk_index(b, hh * HD + t)] = mtts::f2bf(o / L);
+  }
+  if (a.lse && t == 0) a.lse[(int64_t)b * a.heads + hh] = M == -INFINITY ? -INFINITY : (M + log2f(L)) * kLn2;
+}
+
+template <typename T, int HD, int U, bool QP = false>
+__global__ __launch_bounds__(256) void attn_decode1_kernel(MttsAttnFwdArgs a, QProj qp) {
+  __shared__ float sx[QP ? kQpMaxDm : 1], sq[QP ? HD : 1], sred[4];
+  const int bh = blockIdx.x, b = bh / a.heads, hh = bh % a.heads, d0 = threadIdx.x % (HD / 8) * 8;
+  float q[8];
+  if constexpr (QP) {
+    qproj_head<HD>(qp, b, hh, sx, sq, sred);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = sq[d0 + e];
+  } else {
+    ld8((const T*)a.q + b * a.q_bs + hh * HD + d0, q);
+  }
+  float M, L = 0.f, o = 0.f;
+  decode_single_pass<T, HD, U>(a, b, hh, q, 0, a.kv_len, M, L, o);
+  if (threadIdx.x < HD) decode_store_row<T, HD>(a, b, hh, threadIdx.x, M, L, o);
+}
+
+template <typename T, int HD>
+void launch_decode(const MttsAttnFwdArgs* a, hipStream_t st) {
+  const dim3 grid(a->batch * a->heads);
+  const QProj none{};
+  if (a->kv_len <= single_pass_keys(HD, 4))
+    hipLaunchKernelGGL((attn_decode1_kernel<T, HD, 4>), grid, dim3(256), 0, st, *a, none);
+  else if (a->kv_len <= single_pass_keys(HD))
+    hipLaunchKernelGGL((attn_decode1_kernel<T, HD, kDecodeU>), grid, dim3(256), 0, st, *a, none);
+  else
+    hipLaunchKernelGGL((attn_decode_kernel<T, HD>), grid, dim3(256), 0, st, *a);
+}
+
+template <int HD>
+void launch_decode_qp(const MttsAttnFwdArgs* a, const QProj& qp, hipStream_t st) {
+  const dim3 grid(a->batch * a->heads);
+  if (a->kv_len <= single_pass_keys(HD, 4))
+    hipLaunchKernelGGL((attn_decode1_kernel<mtts::bf16_t, HD, 4, true>), grid, dim3(256), 0, st, *a, qp);
+  else
+    hipLaunchKernelGGL((attn_decode1_kernel<mtts::bf16_t, HD, kDecodeU, true>), grid, dim3(256), 0, st, *a, qp);
+}
+
+// ---------------------------------------------------------------------------
+// Long key sides (the 5248-key conditioning of train.py), split over the key
+// axis: workgroup (b, h, c) owns the CK = split_chunk(HD) = 16384 / HD keys of
+// chunk c -- what attn_decode1_kernel<T, HD, 8> holds in registers -- and runs
+// decode_single_pass, the body that kernel runs, on them (all K and V of the
+// chunk loaded before any arithmetic, no online rescaling), leaving one fp32
+// partial (chunk max in log2 units, sum p, HD unnormalised accumulators) in the
+// workspace (a chunk with every key masked: -inf, 0, zeros); the
+// merge launch sums a row's partials in chunk order.  CK depends on the head
+// dim alone, so a row's chunks, and with them every rounding of its result,
+// are the same at any batch size, row index and kv_len.  A row reads only its
+// own n_b = min(kv_lens[b], kv_len) keys: chunks at or past n_b return before
+// any load, key indices past n_b are clamped to the chunk's first key.
+// No atomics, no hand-off inside a launch.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int row_keys(const int32_t* kv_lens, int b, int kv_len) {
+  if (!kv_lens) return kv_len;
+  const int n = kv_lens[b];
+  return n < 0 ? 0 : (n < kv_len ? n : kv_len);
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void attn_decode_split_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens, float* ws,
+                                                                 int nchunk) {
+  const int bh = blockIdx.x, chunk = blockIdx.y, b = bh / a.heads, hh = bh % a.heads;
+  const int n = row_keys(kv_lens, b, a.kv_len), k0 = chunk * split_chunk(HD);
+  if (k0 >= n) return;   // uniform over the workgroup; before any load or barrier
+  float q[8];
+  ld8((const T*)a.q + b * a.q_bs + hh * HD + threadIdx.x % (HD / 8) * 8, q);   // the thread's 8 dims, as the body's
+  float M, L = 0.f, o = 0.f;
+  decode_single_pass<T, HD, kDecodeU>(a, b, hh, q, k0, n, M, L, o);
+  if (threadIdx.x < HD) {
     float* pw = ws + ((int64_t)bh * nchunk + chunk) * (HD + 2);
-    if (threadIdx.x == 0) pw[0] = M, pw[1] = (swl[0] + swl[1]) + (swl[2] + swl[3]);
-    pw[2 + threadIdx.x] = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
+    if (threadIdx.x == 0) pw[0] = M, pw[1] = L;
+    pw[2 + threadIdx.x] = o;
   }
 }
 
@@ -2021,12 +2005,7 @@ __global__ __launch_bounds__(HD < 64 ? 64 : HD) void attn_decode_merge_kernel(Mt
     L += pi[1] * f;
     o += pi[2 + t] * f;
   }
-  // no key (n = 0) or every key masked: L = 0 -> 0/0 = NaN (torch MHA), lse = -inf
-  if (a.out) mtts::stf((T*)a.out + b * a.o_bs + hh * HD + t, o / L);
-  if constexpr (sizeof(T) == 2) {
-    if (a.out_packed) ((mtts::bf16_t*)a.out_packed)[mtts::xpk_index(b, hh * HD + t)] = mtts::f2bf(o / L);
-  }
-  if (a.lse && t == 0) a.lse[(int64_t)b * a.heads + hh] = M == -INFINITY ? -INFINITY : (M + log2f(L)) * kLn2;
+  decode_store_row<T, HD>(a, b, hh, t, M, L, o);   // n = 0: no chunk, L = 0
 }
 
 template <typename T, int HD>
@@ -2039,39 +2018,27 @@ void launch_decode_split(const MttsAttnFwdArgs* a, const int32_t* kv_lens, float
                      (const float*)ws, nchunk);
 }
 
-template <typename T>
-void dispatch_decode_split(const MttsAttnFwdArgs* a, const int32_t* kv_lens, float* ws, hipStream_t st) {
-  switch (a->head_dim) {
-    case 16: launch_decode_split<T, 16>(a, kv_lens, ws, st); break;
-    case 32: launch_decode_split<T, 32>(a, kv_lens, ws, st); break;
-    case 64: launch_decode_split<T, 64>(a, kv_lens, ws, st); break;
-    default: launch_decode_split<T, 128>(a, kv_lens, ws, st); break;
-  }
-}
-
 int64_t decode_split_bytes(int batch, int heads, int head_dim, int kv_len) {
   const int ck = split_chunk(head_dim);
   return (int64_t)batch * heads * ((kv_len + ck - 1) / ck) * (head_dim + 2) * 4;
 }
 
-template <typename T>
-void dispatch_decode(const MttsAttnFwdArgs* a, hipStream_t st) {
-  switch (a->head_dim) {
-    case 16: launch_decode<T, 16>(a, st); break;
-    case 32: launch_decode<T, 32>(a, st); break;
-    case 64: launch_decode<T, 64>(a, st); break;
-    default: launch_decode<T, 128>(a, st); break;
+// f(std::integral_constant<int, head_dim>): the head dim as a compile-time
+// constant.  check_fwd has refused every other value, so default means 128.
+template <typename F>
+void with_head_dim(int head_dim, F&& f) {
+  switch (head_dim) {
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    default: f(std::integral_constant<int, 128>{}); break;
   }
 }
 
-template <typename T>
-void dispatch_fwd(const MttsAttnFwdArgs* a, hipStream_t st) {
-  switch (a->head_dim) {
-    case 16: launch_fwd<T, 16>(a, st); break;
-    case 32: launch_fwd<T, 32>(a, st); break;
-    case 64: launch_fwd<T, 64>(a, st); break;
-    default: launch_fwd<T, 128>(a, st); break;
-  }
+// check_fwd with the packed image standing in for a missing row-major out
+int check_fwd_either_out(MttsAttnFwdArgs c, const char* who) {
+  if (!c.out) { c.out = c.out_packed; c.o_bs = c.o_ls = 0; }
+  return check_fwd(&c, who);
 }
 
 struct BwdPlan {
@@ -2080,18 +2047,23 @@ struct BwdPlan {
   int64_t part_bytes, dq_bytes, delta_bytes;
 };
 
-BwdPlan plan_bwd(int batch, int heads, int head_dim, int q_len, int kv_len, int dtype) {
-  BwdPlan pl{};
-  pl.kg = (dtype == MTTS_F32 && head_dim > 64) ? 64 : 128;
+// Query chunks for a launch that has `wgs` workgroups before chunking: enough
+// to reach 256, at most one per 32-query slice; qchunk / nchunk from that.
+void plan_chunks(BwdPlan& pl, int wgs, int q_len) {
   const int slices = (q_len + 31) / 32;
-  const int base = batch * heads;
-  int nchunk = base >= 256 ? 1 : (256 + base - 1) / base;
+  int nchunk = wgs >= 256 ? 1 : (256 + wgs - 1) / wgs;
   if (mtts::override_of(MTTS_OVR_ATTN_CHUNKS) >= 1) nchunk = mtts::override_of(MTTS_OVR_ATTN_CHUNKS);
   nchunk = nchunk < 1 ? 1 : (nchunk > slices ? (slices > 0 ? slices : 1) : nchunk);
   const int per = (slices + nchunk - 1) / nchunk;
   pl.qchunk = 32 * (per > 0 ? per : 1);
   pl.nchunk = (q_len + pl.qchunk - 1) / pl.qchunk;
   if (pl.nchunk < 1) pl.nchunk = 1;
+}
+
+BwdPlan plan_bwd(int batch, int heads, int head_dim, int q_len, int kv_len, int dtype) {
+  BwdPlan pl{};
+  pl.kg = (dtype == MTTS_F32 && head_dim > 64) ? 64 : 128;
+  const int base = batch * heads;
   const int64_t d = (int64_t)heads * head_dim;
   // split backward (dQ pass + dK/dV pass) for a key side longer than one key
   // group; the dK/dV pass may be chunked over queries into partials.  (For
@@ -2100,19 +2072,12 @@ BwdPlan plan_bwd(int batch, int heads, int head_dim, int q_len, int kv_len, int 
   const int force = mtts::override_of(MTTS_OVR_ATTN_BWD);
   pl.split = force == 2 || (kv_len > pl.kg && force != 1);
   if (pl.split) {
-    const int nkg = (kv_len + pl.kg - 1) / pl.kg;
-    const int wgs = nkg * base;
-    int nc = wgs >= 256 ? 1 : (256 + wgs - 1) / wgs;
-    if (mtts::override_of(MTTS_OVR_ATTN_CHUNKS) >= 1) nc = mtts::override_of(MTTS_OVR_ATTN_CHUNKS);
-    nc = nc < 1 ? 1 : (nc > slices ? (slices > 0 ? slices : 1) : nc);
-    const int per2 = (slices + nc - 1) / nc;
-    pl.qchunk = 32 * (per2 > 0 ? per2 : 1);
-    pl.nchunk = (q_len + pl.qchunk - 1) / pl.qchunk;
-    if (pl.nchunk < 1) pl.nchunk = 1;
+    plan_chunks(pl, (kv_len + pl.kg - 1) / pl.kg * base, q_len);
     pl.part_bytes = pl.nchunk > 1 ? (int64_t)pl.nchunk * batch * kv_len * 2 * d * 4 : 0;
     pl.delta_bytes = ((int64_t)batch * heads * q_len * 4 + 255) / 256 * 256;
     return pl;
   }
+  plan_chunks(pl, base, q_len);
   pl.part_bytes = pl.nchunk > 1 ? (int64_t)pl.nchunk * batch * kv_len * 2 * d * 4 : 0;
   pl.dq_bytes = kv_len > pl.kg ? (int64_t)batch * q_len * d * 4 : 0;
   return pl;
@@ -2155,12 +2120,7 @@ void launch_bwd(const BwdParams& p, bool split, hipStream_t st) {
 
 template <typename T>
 void dispatch_bwd(const BwdParams& p, bool split, hipStream_t st) {
-  switch (p.a.f.head_dim) {
-    case 16: launch_bwd<T, 16>(p, split, st); break;
-    case 32: launch_bwd<T, 32>(p, split, st); break;
-    case 64: launch_bwd<T, 64>(p, split, st); break;
-    default: launch_bwd<T, 128>(p, split, st); break;
-  }
+  with_head_dim(p.a.f.head_dim, [&](auto hd) { launch_bwd<T, hd()>(p, split, st); });
   if (p.nchunk > 1) {
     const int64_t n = (int64_t)p.a.f.batch * p.a.f.kv_len * 2 * p.a.f.heads * p.a.f.head_dim;
     int blocks = (int)((n + 255) / 256);
@@ -2179,16 +2139,17 @@ extern "C" int mtts_attention_fwd(const MttsAttnFwdArgs* a, void* stream) {
              "attention_fwd: a k / v head stride is taken by the single-query kernels only (q_len 1)");
   // the packed image is written by the single-pass decode kernel only
   MTTS_CHECK(!a->out_packed || (a->q_len == 1 && a->dtype == MTTS_BF16 && a->batch <= 32 &&
-                                (a->heads * a->head_dim) % 32 == 0 && a->kv_len <= 8 * (256 / (a->head_dim / 8)) &&
+                                (a->heads * a->head_dim) % 32 == 0 && a->kv_len <= single_pass_keys(a->head_dim) &&
                                 mtts::override_of(MTTS_OVR_ATTN_GENERIC) != 1),
-             "attention_fwd: packed output needs q_len 1, bf16, batch <= 32, kv_len <= %d", 8 * (256 / (a->head_dim / 8)));
+             "attention_fwd: packed output needs q_len 1, bf16, batch <= 32, kv_len <= %d", single_pass_keys(a->head_dim));
   if (a->batch == 0 || a->q_len == 0) return MTTS_OK;
   hipStream_t st = (hipStream_t)stream;
   const bool one = a->q_len == 1 && mtts::override_of(MTTS_OVR_ATTN_GENERIC) != 1;   // decode step: single-query kernel
-  if (a->dtype == MTTS_BF16)
-    one ? dispatch_decode<bf16_t>(a, st) : dispatch_fwd<bf16_t>(a, st);
-  else
-    one ? dispatch_decode<float>(a, st) : dispatch_fwd<float>(a, st);
+  const bool bf = a->dtype == MTTS_BF16;
+  with_head_dim(a->head_dim, [&](auto hd) {
+    if (one) bf ? launch_decode<bf16_t, hd()>(a, st) : launch_decode<float, hd()>(a, st);
+    else bf ? launch_fwd<bf16_t, hd()>(a, st) : launch_fwd<float, hd()>(a, st);
+  });
   MTTS_LAUNCH_CHECK("attention_fwd");
   return MTTS_OK;
 }
@@ -2201,14 +2162,13 @@ extern "C" int mtts_attention_decode_qproj(const MttsAttnQProjArgs* q, void* str
     MttsAttnFwdArgs c = a;
     c.q = q->x;
     c.q_bs = c.q_ls = 0;
-    if (!c.out) { c.out = c.out_packed; c.o_bs = c.o_ls = 0; }
-    int rc = check_fwd(&c, "attention_decode_qproj");
+    int rc = check_fwd_either_out(c, "attention_decode_qproj");
     if (rc) return rc;
   }
-  const int NG = 256 / (a.head_dim / 8);
-  MTTS_CHECK(a.q_len == 1 && a.dtype == MTTS_BF16 && a.kv_len <= 8 * NG && a.batch <= 32 &&
+  MTTS_CHECK(a.q_len == 1 && a.dtype == MTTS_BF16 && a.kv_len <= single_pass_keys(a.head_dim) && a.batch <= 32 &&
                  (a.heads * a.head_dim) % 32 == 0 && (a.head_dim == 64 || a.head_dim == 128),
-             "attention_decode_qproj: q_len 1, bf16, head_dim 64 / 128, batch <= 32, kv_len <= %d", 8 * NG);
+             "attention_decode_qproj: q_len 1, bf16, head_dim 64 / 128, batch <= 32, kv_len <= %d",
+             single_pass_keys(a.head_dim));
   MTTS_CHECK(q->x && q->wq && q->ln_w && q->ln_b, "attention_decode_qproj: null x / wq / ln_w / ln_b");
   MTTS_CHECK(q->d_model > 0 && q->d_model <= kQpMaxDm && q->d_model % 8 == 0 && q->x_rs >= q->d_model &&
                  ((uintptr_t)q->wq % 16) == 0,
@@ -2234,12 +2194,8 @@ extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, voi
   const MttsAttnFwdArgs& a = s->f;
   MTTS_CHECK(a.q_len == 1, "attention_decode_split: q_len %d (the single-query kernels take q_len 1)", a.q_len);
   MTTS_CHECK(a.out || a.out_packed, "attention_decode_split: null out and out_packed");
-  {   // check_fwd with the packed image standing in for a missing row-major out
-    MttsAttnFwdArgs c = a;
-    if (!c.out) { c.out = c.out_packed; c.o_bs = c.o_ls = 0; }
-    int rc = check_fwd(&c, "attention_decode_split");
-    if (rc) return rc;
-  }
+  int rc = check_fwd_either_out(a, "attention_decode_split");
+  if (rc) return rc;
   MTTS_CHECK(a.kv_len >= 1, "attention_decode_split: kv_len %d must be >= 1", a.kv_len);
   MTTS_CHECK(a.kv_hs % 8 == 0 && a.kv_hs >= 0, "attention_decode_split: kv_hs must be a multiple of 8 elements");
   MTTS_CHECK(!a.out_packed || (a.dtype == MTTS_BF16 && a.batch <= 32 && (a.heads * a.head_dim) % 32 == 0),
@@ -2251,10 +2207,11 @@ extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, voi
              "attention_decode_split: workspace of %lld bytes, need %lld (4-byte aligned, "
              "mtts_attention_decode_split_workspace)", (long long)(s->workspace ? s->workspace_bytes : 0), (long long)need);
   hipStream_t st = (hipStream_t)stream;
-  if (a.dtype == MTTS_BF16)
-    dispatch_decode_split<bf16_t>(&a, s->kv_lens, (float*)s->workspace, st);
-  else
-    dispatch_decode_split<float>(&a, s->kv_lens, (float*)s->workspace, st);
+  float* ws = (float*)s->workspace;
+  with_head_dim(a.head_dim, [&](auto hd) {
+    if (a.dtype == MTTS_BF16) launch_decode_split<bf16_t, hd()>(&a, s->kv_lens, ws, st);
+    else launch_decode_split<float, hd()>(&a, s->kv_lens, ws, st);
+  });
   MTTS_LAUNCH_CHECK("attention_decode_split");
   return MTTS_OK;
 }

@@ -385,7 +385,7 @@ class DecodeEngine:
                                  xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"])
             x = ops.gemm_rows(y, w(p, "Wout"), res=x)
             q = ops.gemm_rows(x, w(p, "Wq"), p["bq"], ln=ln(l.norm_cross))
-            o = self._cross(q, p["k"], p["v"], l.cross_attn.num_heads)
+            o = self._attend(q, p, l.cross_attn.num_heads, packed=False)
             x = ops.gemm_rows(o, w(p, "Wo"), p["bo"], res=x)
             f = ops.gemm_rows(x, w(p, "W1"), p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma"], p["beta"]))
             x = ops.gemm_rows(f, w(p, "W2"), p["b2"], res=x)
@@ -398,24 +398,26 @@ class DecodeEngine:
         predicate's to refuse: False, and the attention call raises."""
         return self.ctx["split"] and hd in (16, 32, 64, 128) and S > decode_split_chunk(hd)
 
-    def _cross_split(self, q, k, v, H, packed=False):
-        """The split-key kernel with the context's key counts and its
-        workspace: one allocation per context (every layer's partials have
-        the same shape and the layers run in turn on one stream)."""
+    def _attend(self, q, p, H, packed):
+        """Every step's cross-attention of q (B, d) over the keys of the
+        layer's entry p, and the one place that picks its kernel.  A long key
+        side (_split): the split-key kernel with the context's key counts and
+        its workspace, one allocation per context (every layer's partials
+        have the same shape and the layers run in turn on one stream).  Else
+        a packed step takes the single-pass kernel's packed image, a
+        row-major step the single-query kernels of mtts_attention_fwd.  A
+        packed step reads the head-major copies of K / V."""
         c = self.ctx
-        S = k.shape[2] if k.dim() == 4 else k.shape[1]
-        need = decode_split_workspace(q.shape[0], H, q.shape[1] // H, S)
-        if c["split_ws"] is None or c["split_ws"].numel() < need:
-            c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
-        return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed, workspace=c["split_ws"])
-
-    def _cross(self, q, k, v, H):
-        """The row-major steps' cross-attention of q (B, d): the split-key
-        kernel on a long key side, else the single-query kernels of
-        mtts_attention_fwd."""
-        if self._split(k.shape[1], q.shape[1] // H):
-            return self._cross_split(q, k, v, H)
-        return attention(q[:, None], k, v, H, self.ctx["kpm"])[:, 0]
+        k, v = (p["khm"], p["vhm"]) if packed else (p["k"], p["v"])
+        S, hd = k.shape[-2], q.shape[1] // H
+        if self._split(S, hd):
+            need = decode_split_workspace(q.shape[0], H, hd, S)
+            if c["split_ws"] is None or c["split_ws"].numel() < need:
+                c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
+            return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed, workspace=c["split_ws"])
+        if packed:
+            return attention_decode_packed(q, k, v, H, c["kpm"])
+        return attention(q[:, None], k, v, H, c["kpm"])[:, 0]
 
     def _xpk_ok(self):
         """Every projection packed and every operand shape the packed
@@ -431,7 +433,7 @@ class DecodeEngine:
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
             if (any(p[k].shape[0] % 32 or p[k].shape[1] % 32 for k in names)
-                    or (p["k"].shape[1] > 8 * (256 // (hd // 8)) and not self._split(p["k"].shape[1], hd))
+                    or (p["k"].shape[1] > decode_split_chunk(hd) and not self._split(p["k"].shape[1], hd))
                     or l.mamba.d_inner % 32):
                 return False
         for l, p in zip(self.m.layers, c["layers"]):   # head-major K / V: one contiguous block per (b, h)
@@ -452,7 +454,7 @@ class DecodeEngine:
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
             if (hd not in (64, 128) or ca.embed_dim > 2048 or ca.embed_dim % 8 or B > 32
-                    or p["khm"].shape[2] > 8 * (256 // (hd // 8)) or p["Wq"].stride(0) != ca.embed_dim):
+                    or p["khm"].shape[2] > decode_split_chunk(hd) or p["Wq"].stride(0) != ca.embed_dim):
                 return False
         return True
 
@@ -486,11 +488,7 @@ class DecodeEngine:
                                                   p["vhm"], l.cross_attn.num_heads, c["kpm"])
             else:
                 q = ops.gemm_rows(xp, p["Wq_p"], p["bq"], ln=ln(l.norm_cross))
-                H = l.cross_attn.num_heads
-                if self._split(p["khm"].shape[2], p["khm"].shape[3]):   # long key side: chunks of the row's own keys
-                    o = self._cross_split(q, p["khm"], p["vhm"], H, packed=True)
-                else:
-                    o = attention_decode_packed(q, p["khm"], p["vhm"], H, c["kpm"])
+                o = self._attend(q, p, l.cross_attn.num_heads, packed=True)
             x, xp = ops.gemm_rows(o, p["Wo_p"], p["bo"], res=x, packed_out="also")
             f = ops.gemm_rows(xp, p["W1_p"], p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma_p"], p["beta_p"]),
                               packed_out="only")
@@ -522,7 +520,7 @@ class DecodeEngine:
             h_m = mm_(y, p["Wout"])
             h, x = ops.layer_norm(h_m, l.norm_cross.weight, l.norm_cross.bias, l.norm_cross.eps, res=x)
             q = mm_(h, p["Wq"], p["bq"])
-            o = self._cross(q, p["k"], p["v"], l.cross_attn.num_heads)
+            o = self._attend(q, p, l.cross_attn.num_heads, packed=False)
             a = mm_(o, p["Wo"], p["bo"])
             h, x = ops.layer_norm(a, l.norm_ff.weight, l.norm_ff.bias, l.norm_ff.eps, res=x,
                                   gamma=p["gamma"], beta=p["beta"], rows_per_group=1)

@@ -168,6 +168,31 @@ def test_layouts_and_output_forms_agree(H, hd, dtype):
             assert torch.equal(img.unpack(), row)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("H,hd", SHAPES)
+def test_one_chunk_is_the_single_pass_kernel(H, hd, dtype):
+    """A key side of at most one chunk gives the same bits through the split
+    path and through the single-pass kernel (csrc/attn.hip decode_single_pass
+    is the body of both; the merge of one chunk multiplies by exp2(0) and adds
+    to zero; the U = 4 and U = 8 forms put key j in the same group at the same
+    u, and the extra u add p = 0 times a finite clamped key)."""
+    from mtts.attn_kernels import attention_decode_packed, attention_decode_split, attention_fwd
+    B, d, ng = 3, H * hd, 256 // (hd // 8)
+    assert 8 * ng == _ck(hd)
+    for S in (5, 4 * ng, 4 * ng + 1, 8 * ng):               # the U = 4 edge, the first key of U = 8, a full chunk
+        q, kv, kpm = make(B, 1, S, H, hd, dtype, seed=11 + S % 89)      # the mask leaves every row key 0
+        k, v = kv[..., :d], kv[..., d:]
+        out, lse = attention_decode_split(q[:, 0], k, v, H, kpm, None, want_lse=True)
+        one, one_lse = attention_fwd(q, k, v, H, kpm, want_lse=True)
+        assert torch.equal(out, one[:, 0]) and torch.equal(lse, one_lse[:, :, 0]), S
+        if dtype == torch.bfloat16:
+            khm = k.reshape(B, S, H, hd).permute(0, 2, 1, 3).contiguous()
+            vhm = v.reshape(B, S, H, hd).permute(0, 2, 1, 3).contiguous()
+            for kk, vv in ((k, v), (khm, vhm)):
+                img = attention_decode_split(q[:, 0], kk, vv, H, kpm, None, packed=True)
+                assert torch.equal(attention_decode_packed(q[:, 0], kk, vv, H, kpm).unpack(), img.unpack()), S
+
+
 def _args(B, H, hd, S, dtype, packed=False):
     from mtts import _lib as L
     from mtts.attn_kernels import _fwd_args
