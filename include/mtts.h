@@ -42,7 +42,8 @@ extern "C" {
  * additive in the same way: MttsSampleArgs and mtts_sample_tokens are
  * untouched, and a binding that needs it checks that the symbol resolves.
  * So is its slot form, mtts_sample_tokens_slots: one more symbol on the same
- * struct. */
+ * struct.  So are the token log-probabilities: three symbols that take the
+ * samplers' structs, byte for byte, and one new struct, MttsSampleLogprobOut. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -1009,6 +1010,52 @@ int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream);
  * *unfinished is rewritten as before.
  * ------------------------------------------------------------------------ */
 int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Token log-probabilities (an addition within ABI 15; a binding that needs it
+ * checks that mtts_sample_tokens_slots_lp resolves).  Each sampler above has
+ * a twin that takes the same struct, draws the same token with the same
+ * bookkeeping, and also writes the probability the model gave that token.
+ * For a row that emits a token of its own, let x_v be the value the sampler
+ * compares: the fp32 logit plus the fp32 bias, NaN -> -inf, the repetition
+ * penalty applied (per-row and slot forms), -0 -> +0.  With m = max_v x_v and
+ * t the emitted token,
+ *     logprob = (x_t - m) - log( sum_v exp(x_v - m) )      (fp32; exp(-inf) = 0)
+ * the model's distribution after the request's logit processors (bias,
+ * penalty), at temperature 1 and before top-k / top-p truncation.  It does
+ * not depend on temperature, top_k, top_p, seed or the draw count; greedy
+ * rows get a value as well.
+ *   sum order:   fixed.  With `threads` = 64 for vocab <= 256 and 256 above,
+ *                each thread adds its entries v = tid + threads * j in
+ *                ascending j, then the workgroup's fixed-order reduction;
+ *                correctly implemented expf / logf, not the fast forms.  The
+ *                same row gives the same bits in any row of any launch.
+ *   m not finite: the value is NaN (no finite candidate, where pad_id is
+ *                emitted, and a +inf logit).
+ *   finished at entry, scalar and per-row forms: 0.0 is written wherever
+ *                pad_id is written.
+ *   finished at entry, slot form: 0.0 goes to `logprob` and nothing to
+ *                `logprob_history`: a finished request's values stay until the
+ *                host has taken them, exactly like its tokens.
+ * Outputs, either of which may be NULL (not both):
+ *   logprob (rows,) fp32:   this launch's value.
+ *   logprob_history fp32, row stride lp_ld: written at the column of `history`
+ *                by the same rule -- *step - step0, or draw[r] in the slot
+ *                form, and only when the column lies in [0, hist_cols).
+ *                `history` itself need not be given; hist_cols bounds the
+ *                column either way, and lp_ld >= hist_cols.
+ * Every check of the form fires first, with its message, under the twin's
+ * name; then "no logprob output" and "bad logprob history shape".
+ * ------------------------------------------------------------------------ */
+typedef struct {
+  float* logprob;
+  float* logprob_history;
+  int64_t lp_ld;
+} MttsSampleLogprobOut;
+
+int mtts_sample_tokens_lp(const MttsSampleArgs* a, const MttsSampleLogprobOut* lp, void* stream);
+int mtts_sample_tokens_rows_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp, void* stream);
+int mtts_sample_tokens_slots_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp, void* stream);
 
 #ifdef __cplusplus
 }

@@ -348,7 +348,7 @@ class MambaTTSDecoder(nn.Module):
     def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, prompt_lengths=None, start_token=0,
                  text_mask=None, ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0,
                  logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32, repetition_penalty=None,
-                 repetition_window=64):
+                 repetition_window=64, return_logprobs=False):
         """Generate up to `max_new_tokens` codec tokens on the device
         (mtts/decode.py DecodeEngine.generate): the decode_step loop with the
         draw (temperature, top-k, top-p, reproducible from `seed`) in the HIP
@@ -385,8 +385,16 @@ class MambaTTSDecoder(nn.Module):
         With every one of these a scalar and no penalty the call is the
         scalar path, unchanged.
 
+        return_logprobs: also return, for every token, the log-probability
+        the model gave it: log softmax over the whole vocabulary of the
+        logits after logit_bias and the repetition penalty, at temperature 1
+        and before top-k / top-p -- independent of the sampling settings, for
+        greedy rows too.  Computed in the sampler's launch; no per-token copy.
+
         Returns tokens (B, n) int64 with n <= max(max_new_tokens) and lengths (B,)
-        int64 (tokens up to and including a row's eos_id)."""
+        int64 (tokens up to and including a row's eos_id); with
+        return_logprobs also logprobs (B, n) fp32, 0.0 at and past a row's
+        length."""
         if not self.decode_mode:
             raise RuntimeError("generate runs on the decode engine: set decode_mode to 'graph' or 'eager'")
         if not (text_hidden.is_cuda and z_style.is_cuda):
@@ -399,30 +407,36 @@ class MambaTTSDecoder(nn.Module):
                                      ref_mask=ref_mask, temperature=temperature, top_k=top_k, top_p=top_p,
                                      logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
                                      check_every=check_every, repetition_penalty=repetition_penalty,
-                                     repetition_window=repetition_window)
+                                     repetition_window=repetition_window, return_logprobs=return_logprobs)
 
-    def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64):
+    def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, logprobs=False):
         """A decode session for continuous batching (mtts/session.py
         DecodeSession): `slots` rows over static per-slot buffers, conditioning
         of up to `max_keys` keys per request, one captured graph of step +
         slot sampler.  admit(slot, ...) puts a request into an idle slot,
         run(n) draws n tokens for every live slot, poll() lists the finished
         slots and take(slot) returns a finished request's tokens and frees
-        the slot.  The session owns its buffers and its graph: generate() and
-        decode_step before, during and after it behave as without one."""
+        the slot.  logprobs=True (decided here, with the capture): the session
+        records every token's log-probability as generate(return_logprobs=True)
+        does, and take(slot, return_logprobs=True) returns them.  The session
+        owns its buffers and its graph: generate() and decode_step before,
+        during and after it behave as without one."""
         if not self.decode_mode:
             raise RuntimeError("open_session runs on the decode engine: set decode_mode to 'graph' or 'eager'")
         from mtts.session import DecodeSession
         return DecodeSession(self, slots, max_keys, eos_id=eos_id, pad_id=pad_id,
-                             repetition_window=repetition_window, use_graph=self.decode_mode == "graph")
+                             repetition_window=repetition_window, use_graph=self.decode_mode == "graph",
+                             logprobs=logprobs)
 
     def generate_requests(self, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                          repetition_window=64):
+                          repetition_window=64, return_logprobs=False):
         """A queue of requests through one session of `slots` rows, refilled
         as rows finish (mtts/session.py generate_requests, by the policy of
         mtts.session.plan_slots).  `requests`: dicts of admit's arguments.
         Returns (token tensors in request order, the slot of every request,
-        the number of replays made)."""
+        the number of replays made); with return_logprobs a fourth element,
+        the requests' log-probability tensors."""
         from mtts.session import generate_requests
         return generate_requests(self, requests, slots=slots, max_keys=max_keys, check_every=check_every,
-                                 eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window)
+                                 eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
+                                 return_logprobs=return_logprobs)

@@ -113,6 +113,10 @@ class SampleRowsArgs(C.Structure):
                 ("length", vp), ("unfinished", vp)]
 
 
+class SampleLogprobOut(C.Structure):
+    _fields_ = [("logprob", vp), ("logprob_history", vp), ("lp_ld", i64)]
+
+
 class RowMap(C.Structure):
     _fields_ = [("ptr", vp), ("seg_rows", i64), ("seg_stride", i64), ("row_stride", i64), ("halo_c", i32),
                 ("halo_p", i32)]
@@ -231,6 +235,9 @@ _SIGS = {
     "mtts_sample_tokens": ([C.POINTER(SampleArgs), vp], i32),
     "mtts_sample_tokens_rows": ([C.POINTER(SampleRowsArgs), vp], i32),
     "mtts_sample_tokens_slots": ([C.POINTER(SampleRowsArgs), vp], i32),
+    "mtts_sample_tokens_lp": ([C.POINTER(SampleArgs), C.POINTER(SampleLogprobOut), vp], i32),
+    "mtts_sample_tokens_rows_lp": ([C.POINTER(SampleRowsArgs), C.POINTER(SampleLogprobOut), vp], i32),
+    "mtts_sample_tokens_slots_lp": ([C.POINTER(SampleRowsArgs), C.POINTER(SampleLogprobOut), vp], i32),
 }
 
 _lib = None
@@ -250,7 +257,8 @@ def lib():
                           ("mtts_sample_tokens_rows", "per-row sampling"),
                           ("mtts_sample_tokens_slots", "decode sessions"),
                           ("mtts_gemm_grouped_rounds", "round-filling weight gradients"),
-                          ("mtts_attention_decode_split", "long-conditioning decode")):
+                          ("mtts_attention_decode_split", "long-conditioning decode"),
+                          ("mtts_sample_tokens_slots_lp", "token log-probabilities")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "
@@ -270,11 +278,11 @@ def exported_symbols():
     return list(_SIGS)
 
 
-def call(name, args):
-    """Invoke ``name(&args, current_stream)``; raise on error."""
+def call(name, args, *more):
+    """Invoke ``name(&args, [&more...,] current_stream)``; raise on error."""
     L = lib()
     stream = torch.cuda.current_stream().cuda_stream
-    rc = getattr(L, name)(C.byref(args), C.c_void_p(stream))
+    rc = getattr(L, name)(C.byref(args), *[C.byref(m) for m in more], C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {L.mtts_last_error().decode()}")
 

@@ -51,6 +51,15 @@
 // in check_sample_rows_args), one dtype x wave-count launch switch and one
 // launch behind the sampler (launch_sample, sample_advance_kernel<kSlots>).
 // An entry point holds its name and the few checks that are its alone.
+//
+// Token log-probabilities (mtts_sample_tokens*_lp, include/mtts.h): the same
+// kernel with a fourth trait, kLogprob, whose parameter struct carries the two
+// output pointers behind the form's own arguments.  Once the token is known
+// the row is walked once more -- exp(x_v - m) summed per thread in the order of
+// every other pass, one block_sum, and thread 0 forms (x_t - m) - log(sum) --
+// on the row as load() made it (bias, NaN fold, penalty), at temperature 1 and
+// before any truncation.  The instantiations without the trait compile none of
+// it and keep their argument layout.
 #include "common.h"
 
 #include <math.h>
@@ -143,16 +152,24 @@ struct SampleParams {
   MttsSampleArgs a;
   static constexpr bool kRows = false;
   static constexpr bool kSlots = false;
+  static constexpr bool kLogprob = false;
 };
 struct SampleRowsParams {   // the per-row form: controls read from device arrays (mtts_sample_tokens_rows)
   MttsSampleRowsArgs a;
   static constexpr bool kRows = true;
   static constexpr bool kSlots = false;
+  static constexpr bool kLogprob = false;
 };
 struct SampleSlotsParams {  // the slot form: the per-row form on the row's own history column (mtts_sample_tokens_slots)
   MttsSampleRowsArgs a;
   static constexpr bool kRows = true;
   static constexpr bool kSlots = true;
+  static constexpr bool kLogprob = false;
+};
+template <typename P>
+struct WithLogprob : P {    // P's form that also writes the token's log-probability (mtts_sample_tokens*_lp)
+  MttsSampleLogprobOut lp;
+  static constexpr bool kLogprob = true;
 };
 
 // The per-row form's penalty window as a set: open addressing over kWinSlots
@@ -187,6 +204,7 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   constexpr int kCache = NW == 1 ? kSampleWaveV : kSampleCache;
   constexpr bool kRows = P::kRows;
   constexpr bool kSlots = P::kSlots;
+  constexpr bool kLogprob = P::kLogprob;
   const auto& p = prm.a;
   __shared__ float xs[kCache];
   __shared__ float es[kCache];
@@ -204,6 +222,13 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
   int64_t* const hist = (p.history && col >= 0 && col < p.hist_cols) ? p.history + (int64_t)row * p.hist_ld + col
                                                                      : nullptr;
   int64_t* const tok_out = p.tokens + (int64_t)row * p.tok_stride;
+  float* lp_out = nullptr;    // this launch's log-probability and its history column: the token's column, by the same rule
+  float* lp_hist = nullptr;
+  if constexpr (kLogprob) {
+    if (prm.lp.logprob) lp_out = prm.lp.logprob + row;
+    if (prm.lp.logprob_history && col >= 0 && col < p.hist_cols)
+      lp_hist = prm.lp.logprob_history + (int64_t)row * prm.lp.lp_ld + col;
+  }
   // this row's controls: kernel arguments, or (per-row form) device arrays with
   // the header's effective rules, so that no value can index or loop out of range.
   // All read here, the length cap included, in one batch of loads.
@@ -228,6 +253,12 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
       *tok_out = p.pad_id;
       if constexpr (!kSlots) {   // a slot keeps its finished request's tokens until the host takes them
         if (hist) *hist = p.pad_id;
+      }
+      if constexpr (kLogprob) {   // 0.0 wherever pad_id went
+        if (lp_out) *lp_out = 0.f;
+        if constexpr (!kSlots) {
+          if (lp_hist) *lp_hist = 0.f;
+        }
       }
     }
     return;
@@ -342,6 +373,24 @@ __global__ __launch_bounds__(NW * 64) void sample_kernel(const P prm) {
     pick = block_red<NW>(pick, OpMax(), slots, phase);
     token = (int64_t)(uint32_t)~(uint32_t)pick;   // the row maximum is always kept: pick != 0
   }
+  if constexpr (kLogprob) {
+    // log softmax(x)[token] at temperature 1 over the whole row; m not finite (no
+    // finite candidate, or a +inf logit): NaN.  Before the bookkeeping below.
+    float lp = __builtin_nanf("");
+    if (m > -INFINITY && m < INFINITY) {
+      float z = 0.f;
+      for (int v = tid; v < V; v += kThreads) z += expf(X(v) - m);   // exp(-inf) = 0
+      z = block_sum<NW>(z, slots, phase);
+      // xs[token] was staged by another thread: four waves have passed the
+      // barrier of the sum above since, one wave has met none yet
+      if constexpr (NW == 1) block_sync();
+      if (tid == 0) lp = (X((int)token) - m) - logf(z);
+    }
+    if (tid == 0) {
+      if (lp_out) *lp_out = lp;
+      if (lp_hist) *lp_hist = lp;
+    }
+  }
   if (tid == 0) {
     *tok_out = token;
     if (hist) *hist = token;
@@ -423,19 +472,41 @@ int check_sample_rows_args(const MttsSampleRowsArgs* a, const char* name) {
   });
 }
 
-// The sampler for P's form (one wave up to kSampleWaveV entries, else four) and,
-// when asked for, the launch behind it.
-template <typename P, typename A>
-int launch_sample(const A* a, const char* name, hipStream_t st) {
-  P prm;
-  prm.a = *a;
-  const bool f32 = a->dtype == MTTS_F32;
-  if (a->vocab <= kSampleWaveV) {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, P>), dim3(a->rows), dim3(64), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, P>), dim3(a->rows), dim3(64), 0, st, prm);
+// The _lp entry points' own checks, behind every check of the form they extend.
+template <typename A>
+int check_logprob_out(const A* a, const MttsSampleLogprobOut* lp, const char* name) {
+  MTTS_CHECK(lp && (lp->logprob || lp->logprob_history), "%s: no logprob output", name);
+  MTTS_CHECK(!lp->logprob_history || lp->lp_ld >= a->hist_cols, "%s: bad logprob history shape", name);
+  return MTTS_OK;
+}
+
+// One dtype x wave-count switch (one wave up to kSampleWaveV entries, else four).
+template <typename P>
+void launch_sample_kernel(const P& prm, hipStream_t st) {
+  const bool f32 = prm.a.dtype == MTTS_F32;
+  const dim3 grid(prm.a.rows);
+  if (prm.a.vocab <= kSampleWaveV) {
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 1, P>), grid, dim3(64), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 1, P>), grid, dim3(64), 0, st, prm);
   } else {
-    if (f32) hipLaunchKernelGGL((sample_kernel<float, 4, P>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
-    else hipLaunchKernelGGL((sample_kernel<bf16_t, 4, P>), dim3(a->rows), dim3(kSampleThreads), 0, st, prm);
+    if (f32) hipLaunchKernelGGL((sample_kernel<float, 4, P>), grid, dim3(kSampleThreads), 0, st, prm);
+    else hipLaunchKernelGGL((sample_kernel<bf16_t, 4, P>), grid, dim3(kSampleThreads), 0, st, prm);
+  }
+}
+
+// The sampler for P's form -- with `lp`, the instantiation that also writes the
+// log-probabilities -- and, when asked for, the launch behind it.
+template <typename P, typename A>
+int launch_sample(const A* a, const char* name, hipStream_t st, const MttsSampleLogprobOut* lp = nullptr) {
+  if (lp) {
+    WithLogprob<P> prm;
+    prm.a = *a;
+    prm.lp = *lp;
+    launch_sample_kernel(prm, st);
+  } else {
+    P prm;
+    prm.a = *a;
+    launch_sample_kernel(prm, st);
   }
   MTTS_LAUNCH_CHECK(name);
   if (a->advance || a->unfinished) {
@@ -451,8 +522,10 @@ int launch_sample(const A* a, const char* name, hipStream_t st) {
 
 using namespace mtts;
 
-extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
-  const char* const name = "sample_tokens";
+// Each form's entry point and its _lp twin share one body: `want_lp` adds the
+// two checks of the outputs behind all of the form's own.
+static int sample_tokens_entry(const MttsSampleArgs* a, const char* name, bool want_lp,
+                               const MttsSampleLogprobOut* lp, void* stream) {
   const int s = check_sample_args(a, name, [=]() -> int {
     MTTS_CHECK(a->temperature >= 0.f, "%s: temperature=%f must be >= 0", name, (double)a->temperature);
     MTTS_CHECK(a->top_k >= 0, "%s: top_k=%d must be >= 0", name, a->top_k);
@@ -462,21 +535,48 @@ extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
   if (s) return s;
   MTTS_CHECK(!a->advance || a->step, "%s: advance needs step", name);
   MTTS_CHECK(a->pos_rows >= 0, "%s: pos_rows=%d must be >= 0", name, a->pos_rows);
-  return launch_sample<SampleParams>(a, name, (hipStream_t)stream);
+  if (want_lp)
+    if (const int e = check_logprob_out(a, lp, name)) return e;
+  return launch_sample<SampleParams>(a, name, (hipStream_t)stream, want_lp ? lp : nullptr);
 }
 
-extern "C" int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream) {
-  const char* const name = "sample_tokens_rows";
+static int sample_tokens_rows_entry(const MttsSampleRowsArgs* a, const char* name, bool want_lp,
+                                    const MttsSampleLogprobOut* lp, void* stream) {
   if (const int s = check_sample_rows_args(a, name)) return s;
   MTTS_CHECK(!a->advance || a->step, "%s: advance needs step", name);
   MTTS_CHECK(a->pos_rows >= 0, "%s: pos_rows=%d must be >= 0", name, a->pos_rows);
-  return launch_sample<SampleRowsParams>(a, name, (hipStream_t)stream);
+  if (want_lp)
+    if (const int e = check_logprob_out(a, lp, name)) return e;
+  return launch_sample<SampleRowsParams>(a, name, (hipStream_t)stream, want_lp ? lp : nullptr);
 }
 
-extern "C" int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream) {
-  const char* const name = "sample_tokens_slots";
+static int sample_tokens_slots_entry(const MttsSampleRowsArgs* a, const char* name, bool want_lp,
+                                     const MttsSampleLogprobOut* lp, void* stream) {
   if (const int s = check_sample_rows_args(a, name)) return s;
   MTTS_CHECK(!(a->advance && a->pos) || a->pos_rows == 0 || a->pos_rows == a->rows,
              "%s: pos_rows=%d must be 0 or rows=%d", name, a->pos_rows, a->rows);
-  return launch_sample<SampleSlotsParams>(a, name, (hipStream_t)stream);
+  if (want_lp)
+    if (const int e = check_logprob_out(a, lp, name)) return e;
+  return launch_sample<SampleSlotsParams>(a, name, (hipStream_t)stream, want_lp ? lp : nullptr);
+}
+
+extern "C" int mtts_sample_tokens(const MttsSampleArgs* a, void* stream) {
+  return sample_tokens_entry(a, "sample_tokens", false, nullptr, stream);
+}
+extern "C" int mtts_sample_tokens_rows(const MttsSampleRowsArgs* a, void* stream) {
+  return sample_tokens_rows_entry(a, "sample_tokens_rows", false, nullptr, stream);
+}
+extern "C" int mtts_sample_tokens_slots(const MttsSampleRowsArgs* a, void* stream) {
+  return sample_tokens_slots_entry(a, "sample_tokens_slots", false, nullptr, stream);
+}
+extern "C" int mtts_sample_tokens_lp(const MttsSampleArgs* a, const MttsSampleLogprobOut* lp, void* stream) {
+  return sample_tokens_entry(a, "sample_tokens_lp", true, lp, stream);
+}
+extern "C" int mtts_sample_tokens_rows_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp,
+                                          void* stream) {
+  return sample_tokens_rows_entry(a, "sample_tokens_rows_lp", true, lp, stream);
+}
+extern "C" int mtts_sample_tokens_slots_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp,
+                                           void* stream) {
+  return sample_tokens_slots_entry(a, "sample_tokens_slots_lp", true, lp, stream);
 }

@@ -158,11 +158,13 @@ def _check_request(m, B, n_new, prompt_tokens, start_token, logit_bias, pad_id, 
     return prompt_tokens, Tp, lens
 
 
-def sampler_buffers(B, V, cap, dev):
+def sampler_buffers(B, V, cap, dev, logprobs=False):
     """The per-row sampler's controls and history for B rows of at most `cap`
     tokens, as device buffers a captured launch reads at run time: generate()'s
-    and a decode session's."""
-    return dict(temperature=torch.zeros(B, dtype=torch.float32, device=dev),
+    and a decode session's.  logprobs: also `lp_hist`, the fp32 (B, cap)
+    history of the emitted tokens' log-probabilities."""
+    lp = dict(lp_hist=torch.zeros(B, cap, dtype=torch.float32, device=dev)) if logprobs else {}
+    return dict(lp, temperature=torch.zeros(B, dtype=torch.float32, device=dev),
                 top_k=torch.zeros(B, dtype=torch.int32, device=dev),
                 top_p=torch.ones(B, dtype=torch.float32, device=dev),
                 row_seed=torch.zeros(B, dtype=torch.int64, device=dev),
@@ -195,16 +197,34 @@ def capture_graph(body, restore):
     return g, out
 
 
-def _proj_blas(x, w, b=None, act=None):
+BLAS_ROWS = 32   # with log-probabilities: the generic step's projections of fewer rows run as this many
+
+
+def _proj_blas(x, w, b=None, act=None, rows=0):
+    """A projection of the generic step on the BLAS GEMM.  The library picks
+    its tiling, and with it the order of every sum, by the GEMM's shape, so a
+    row's result depends on how many rows share the step (measured: the fp32
+    logits of one request differ by 2e-6 between 20 rows and 1).  `rows` > 0
+    (generate(return_logprobs=True) and sessions opened with logprobs=True
+    only): fewer rows than that run as exactly `rows`, zero rows appended --
+    one shape, so a request's logits, and the log-probabilities made of them,
+    are the same bits in a session of any size and in generate() on the
+    request alone, as on the fused step.  It costs one pad launch per
+    projection (profiles/sample_logprobs_ab.txt).  Every other caller passes
+    0 and runs the GEMM as it comes, as before."""
+    M = x.shape[0]
+    if M < rows:
+        x = F.pad(x, (0, 0, 0, rows - M))
     y = x @ w.t() if b is None else torch.addmm(b, x, w.t())
-    return F.gelu(y) if act == "gelu" else y
+    y = F.gelu(y) if act == "gelu" else y
+    return y[:M] if M < rows else y
 
 
-def _proj_rows(x, w, b=None, act=None):
+def _proj_rows(x, w, b=None, act=None, rows=0):
     """HIP skinny GEMM (csrc/rows.hip) for the <= 32-row decode projections."""
     if ops.gemm_rows_ok(x, w):
         return ops.gemm_rows(x, w, b, act)
-    return _proj_blas(x, w, b, act)
+    return _proj_blas(x, w, b, act, rows)
 
 
 class DecodeEngine:
@@ -495,13 +515,27 @@ class DecodeEngine:
             x, xp = ops.gemm_rows(f, p["W2_p"], p["b2"], res=x, packed_out="also")
         return ops.gemm_rows(xp, c["Wh_p"], c["bh"], ln=ln(m.norm_out))[:, None]
 
+    def step_fn(self, logprobs):
+        """The step generate() and a session run: the fused step, or the
+        generic one -- with log-probabilities asked for, its BLAS projections
+        at BLAS_ROWS rows, so that the values do not depend on the row count;
+        without, exactly as decode_step runs it."""
+        if self.fused:
+            return self._step_rows
+        if not logprobs:
+            return self._step
+        return lambda tok, pos, states: self._step(tok, pos, states, rows=BLAS_ROWS)
+
     # -- one step, eager -----------------------------------------------------
-    def _step(self, tok, pos, states):
+    def _step(self, tok, pos, states, rows=0):
         m, c = self.m, self.ctx
         cd = c["cd"]
         x = (F.embedding(tok, m.token_embed.weight) + F.embedding(pos, m.pos_embed.weight)[:, None]).to(cd)
         x = x.view(c["B"], -1)                                               # (B, d)
-        mm_ = _proj_rows if (self.use_rows and cd == torch.bfloat16) else _proj_blas
+        proj = _proj_rows if (self.use_rows and cd == torch.bfloat16) else _proj_blas
+
+        def mm_(x, w, b=None, act=None):   # rows > 0: the BLAS projections at that fixed row count (_proj_blas)
+            return proj(x, w, b, act, rows)
         pending = None
         for i, (l, p) in enumerate(zip(m.layers, c["layers"])):
             conv_state, ssm_state = states[i]
@@ -656,15 +690,19 @@ class DecodeEngine:
         return self.out_buf.clone(), list(self.states)
 
     # -- generation ------------------------------------------------------------
-    def _gen_buffers(self, B, V, dev):
+    def _gen_buffers(self, B, V, dev, logprobs=False):
         """Device-resident generation state, made once per context (before any
         capture): seed / step counters, the token history, end-of-sequence
         bookkeeping, the logit bias, pinned slots for the early-stop polls and
-        the per-row sampler's controls (filled per call, read at run time)."""
+        the per-row sampler's controls (filled per call, read at run time).
+        The log-probability history joins them at the first call that asks
+        for it, before that call's capture."""
+        cap = self.m.pos_embed.num_embeddings
+        if self.gen is not None and logprobs and "lp_hist" not in self.gen:
+            self.gen["lp_hist"] = sampler_buffers(B, V, cap, dev, logprobs=True)["lp_hist"]
         if self.gen is None:
-            cap = self.m.pos_embed.num_embeddings
             self.gen = dict(
-                sampler_buffers(B, V, cap, dev),
+                sampler_buffers(B, V, cap, dev, logprobs),
                 seed=torch.zeros(1, dtype=torch.int64, device=dev), step=torch.zeros(1, dtype=torch.int32, device=dev),
                 finished=torch.zeros(B, dtype=torch.int32, device=dev),
                 length=torch.zeros(B, dtype=torch.int64, device=dev),
@@ -734,7 +772,7 @@ class DecodeEngine:
     def generate(self, text_hidden, z_style, max_new_tokens, prompt_tokens=None, start_token=0, text_mask=None,
                  ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, eos_id=None,
                  pad_id=0, seed=0, check_every=32, prompt_lengths=None, repetition_penalty=None,
-                 repetition_window=64):
+                 repetition_window=64, return_logprobs=False):
         """Autoregressive generation on the device: each new token is one
         replay of a hipGraph holding the decode step and the sampler
         (csrc/sample.hip), which writes the token buffer the next step embeds,
@@ -776,7 +814,22 @@ class DecodeEngine:
         row stops at its own max_new_tokens (pad_id afterwards); the loop runs
         to the largest, and the early-stop poll also runs when the caps differ.
 
-        Returns tokens (B, n) int64, n <= max(max_new_tokens), and lengths (B,)."""
+        return_logprobs: the sampler launch also records, next to every token,
+        the log-probability the model gave it (include/mtts.h,
+        MttsSampleLogprobOut: after logit_bias and the repetition penalty, at
+        temperature 1, before top-k / top-p), the first draw from a prompt's
+        prefill logits included.  Such a call has graphs of its own (the key
+        gains one element); without the flag nothing differs from before.
+        On the generic (non-fused) step a call with the flag runs the BLAS
+        projections at a fixed row count (_proj_blas, step_fn), so that the
+        values do not depend on the batch size; its logits then differ from
+        those of a call without the flag by rounding (order 1e-6), and a token
+        can differ where two candidates are that close.  On the fused bf16
+        step both calls compute the same bits.
+
+        Returns tokens (B, n) int64, n <= max(max_new_tokens), and lengths (B,);
+        with return_logprobs also logprobs (B, n) fp32, 0.0 at and past a row's
+        length."""
         m = self.m
         V = m.head.weight.shape[0]
         B = text_hidden.shape[0]
@@ -802,14 +855,16 @@ class DecodeEngine:
         self.check_errors()                         # a flag left by earlier decode_steps is theirs
         conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
         self._prepare(conds, (B, 1), dev)
-        g = self._gen_buffers(B, V, dev)
-        stepfn = self._step_rows if self.fused else self._step
+        g = self._gen_buffers(B, V, dev, bool(return_logprobs))
+        stepfn = self.step_fn(bool(return_logprobs))
         eos = None if eos_id is None else int(eos_id)
 
         def draw(logits):
             common = dict(logit_bias=g["bias"], step=g["step"], advance=True, out=self.tok_buf, history=g["hist"],
                           eos_id=eos, pad_id=int(pad_id), finished=g["finished"], length=g["length"],
                           unfinished=g["unfinished"], pos=self.pos32 if self.fused else None)
+            if return_logprobs:
+                common["logprob_history"] = g["lp_hist"]
             if per_row:
                 ops.sample_tokens_rows(logits, temperature=g["temperature"], top_k=g["top_k"], top_p=g["top_p"],
                                        seed=g["row_seed"], draw=g["draw"], penalty=g["penalty"],
@@ -834,6 +889,8 @@ class DecodeEngine:
         if self.use_graph:
             key = (("rows", eos, int(pad_id), ctl["window"]) if per_row
                    else (float(temperature), int(top_k), float(top_p), eos, int(pad_id)))
+            if return_logprobs:
+                key += ("logprobs",)
             gr = self.gen_graphs.get(key)
             if gr is None:
                 g["bias"].zero_()
@@ -891,4 +948,6 @@ class DecodeEngine:
         n = issued
         if poll and int(g["unfinished"].item()) == 0:
             n = int(lengths.max())                  # trimmed at the step where every row had finished
+        if return_logprobs:
+            return g["hist"][:, :n].clone(), lengths, g["lp_hist"][:, :n].clone()
         return g["hist"][:, :n].clone(), lengths

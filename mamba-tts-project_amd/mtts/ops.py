@@ -905,9 +905,39 @@ def _sample_io(a, fn, logits, logit_bias, step, advance, out, history, step0, eo
     return out, step_t
 
 
+def _sample_call(a, fn, logits, history, logprob, logprob_history):
+    """Launch mtts_<fn> on the filled struct `a`; with either log-probability
+    output, its twin mtts_<fn>_lp with the outputs checked here: logprob a
+    contiguous (rows,) fp32 tensor, logprob_history (rows, n) fp32 with unit
+    column stride, n the history's when that is given (else n bounds the
+    column, as hist_cols)."""
+    if logprob is None and logprob_history is None:
+        L.call("mtts_" + fn, a)
+        return
+    rows, dev = logits.shape[0], logits.device
+    o = L.SampleLogprobOut()
+    t = logprob
+    if t is not None:
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != (rows,)
+                or not t.is_contiguous()):
+            raise ValueError(f"{fn}: logprob must be a contiguous ({rows},) {torch.float32} tensor on {dev}")
+        o.logprob = t.data_ptr()
+    t = logprob_history
+    if t is not None:
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 2
+                or t.shape[0] != rows or t.stride(1) != 1 or (rows > 1 and t.stride(0) < t.shape[1])
+                or (history is not None and t.shape[1] != history.shape[1])):
+            raise ValueError(f"{fn}: logprob_history must be (rows, n) {torch.float32} on {dev} with unit column "
+                             "stride and rows that do not overlap, n as history's")
+        o.logprob_history, o.lp_ld = t.data_ptr(), max(t.stride(0), t.shape[1])
+        if history is None:
+            a.hist_cols = t.shape[1]
+    L.call("mtts_" + fn + "_lp", a, o)
+
+
 def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, seed, step, advance=False,
                   out=None, history=None, step0=0, eos_id=None, pad_id=0, finished=None, length=None,
-                  unfinished=None, pos=None):
+                  unfinished=None, pos=None, logprob=None, logprob_history=None):
     """One token per row of `logits` (rows, V) fp32 / bf16 (unit column
     stride, any row stride) in one HIP launch: x = logits + logit_bias,
     greedy for temperature == 0, else top-k, then top-p on softmax(x / T),
@@ -926,6 +956,12 @@ def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=Non
     unfinished (1,) int32: end-of-sequence bookkeeping -- a finished row emits
     pad_id and keeps its length, a row becomes finished on emitting eos_id,
     and `unfinished` is rewritten with the number of rows still running.
+    logprob (rows,) fp32 / logprob_history (rows, n) fp32, n as history's:
+    the log-probability of the emitted token under softmax(x) -- temperature
+    1, before top-k / top-p; 0.0 where a finished row gets pad_id, NaN for a
+    row without a finite maximum -- and the same value in the history's
+    column (include/mtts.h, MttsSampleLogprobOut).  With both None the launch
+    is the one it always was.
     Returns the tokens."""
     if temperature < 0 or top_k < 0 or not 0 < top_p <= 1:
         raise ValueError("sample_tokens: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
@@ -935,7 +971,7 @@ def sample_tokens(logits, *, temperature=1.0, top_k=0, top_p=1.0, logit_bias=Non
     a.top_k, a.temperature, a.top_p = int(top_k), float(temperature), float(top_p)
     seed_t = _dev_scalar(seed, torch.int64, logits.device, "seed")
     a.seed = seed_t.data_ptr()
-    L.call("mtts_sample_tokens", a)
+    _sample_call(a, "sample_tokens", logits, history, logprob, logprob_history)
     return out
 
 
@@ -962,7 +998,7 @@ def row_seeds(seed, rows):
     return out
 
 
-def _sample_rows(fn, logits, controls, window, io, one_row_pos=False):
+def _sample_rows(fn, logits, controls, window, io, one_row_pos=False, logprob=None, logprob_history=None):
     """What the per-row and the slot form share (`fn` names the caller in
     every message and, behind mtts_, the symbol called): _sample_io on `io`,
     its keyword arguments; the seven per-row arrays `controls` (temperature,
@@ -993,13 +1029,13 @@ def _sample_rows(fn, logits, controls, window, io, one_row_pos=False):
     if max_length is not None and (io["finished"] is None or io["length"] is None):
         raise ValueError(f"{fn}: max_length needs finished and length")
     a.window = window
-    L.call("mtts_" + fn, a)
+    _sample_call(a, fn, logits, io["history"], logprob, logprob_history)
     return out
 
 
 def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
                        logit_bias=None, step, advance=False, out=None, history=None, step0=0, eos_id=None, pad_id=0,
-                       finished=None, length=None, unfinished=None, pos=None):
+                       finished=None, length=None, unfinished=None, pos=None, logprob=None, logprob_history=None):
     """sample_tokens with per-row controls read from device memory at run
     time (include/mtts.h, MttsSampleRowsArgs, has the exact definition): rows
     of one launch, and replays of one captured launch, may differ in all of
@@ -1015,16 +1051,17 @@ def sample_tokens_rows(logits, *, temperature, top_k, top_p, seed, draw, penalty
     window (int, 0..256): the penalty applies once to each distinct id among
     the row's last min(window, draw[r], step - step0) history columns (ids
     outside [0, V) are skipped); it needs `history`.
-    Everything else is as in sample_tokens.  No device value is read here."""
+    Everything else is as in sample_tokens -- logprob / logprob_history are of
+    the penalised row.  No device value is read here."""
     return _sample_rows("sample_tokens_rows", logits, (temperature, top_k, top_p, seed, draw, penalty, max_length), window,
                         dict(logit_bias=logit_bias, step=step, advance=advance, out=out, history=history, step0=step0,
                              eos_id=eos_id, pad_id=pad_id, finished=finished, length=length, unfinished=unfinished,
-                             pos=pos))
+                             pos=pos), logprob=logprob, logprob_history=logprob_history)
 
 
 def sample_tokens_slots(logits, *, temperature, top_k, top_p, seed, draw, penalty=None, window=0, max_length=None,
                         logit_bias=None, step=None, advance=False, out=None, history=None, eos_id=None, pad_id=0,
-                        finished=None, length=None, unfinished=None, pos=None):
+                        finished=None, length=None, unfinished=None, pos=None, logprob=None, logprob_history=None):
     """sample_tokens_rows for the rows ("slots") of a decode session, whose
     requests were admitted at different times (include/mtts.h,
     mtts_sample_tokens_slots, has the exact definition).  It differs in this:
@@ -1032,12 +1069,14 @@ def sample_tokens_slots(logits, *, temperature, top_k, top_p, seed, draw, penalt
     history[r, draw[r]] and the penalty covers the last min(window, draw[r])
     columns before it -- so there is no step0 and `step` is optional (None, or
     a one-element int32 device tensor that advance=True still increments);
-    a row finished at entry gets pad_id in `out` and keeps its history, draw
-    and length; and advance=True with per-row `pos` moves only the rows that
-    are unfinished after the draw.  No device value is read here."""
+    a row finished at entry gets pad_id in `out` (and 0.0 in `logprob`) and
+    keeps its history, its logprob_history, draw and length; and advance=True
+    with per-row `pos` moves only the rows that are unfinished after the draw.
+    logprob_history's column is draw[r] too.  No device value is read here."""
     if step is not None and not isinstance(step, torch.Tensor):
         raise ValueError("sample_tokens_slots: step must be None or a one-element int32 device tensor")
     return _sample_rows("sample_tokens_slots", logits, (temperature, top_k, top_p, seed, draw, penalty, max_length),
                         window, dict(logit_bias=logit_bias, step=step, advance=advance, out=out, history=history, step0=0,
                                      eos_id=eos_id, pad_id=pad_id, finished=finished, length=length,
-                                     unfinished=unfinished, pos=pos), one_row_pos=True)
+                                     unfinished=unfinished, pos=pos), one_row_pos=True, logprob=logprob,
+                        logprob_history=logprob_history)

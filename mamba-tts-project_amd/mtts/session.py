@@ -65,7 +65,8 @@ class DecodeSession:
     CAPTURES = 0        # graphs captured by every session of the process (tests count them)
 
     @torch.no_grad()
-    def __init__(self, model, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, use_graph=True):
+    def __init__(self, model, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, use_graph=True,
+                 logprobs=False):
         m = self.m = model
         V = m.head.weight.shape[0]
         slots, max_keys = int(slots), int(max_keys)
@@ -79,6 +80,7 @@ class DecodeSession:
         self.slots, self.max_keys, self.V = slots, max_keys, V
         self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), repetition_window
         self.use_graph = bool(use_graph)
+        self.logprobs = bool(logprobs)                      # decided here: it selects the one capture
         self.dev = dev
         d = m.token_embed.weight.shape[1]
         cd = self.cd = m._cd()
@@ -114,7 +116,7 @@ class DecodeSession:
         self.length = self._raw[:8 * slots].view(torch.int64)
         self.finished = self._raw[8 * slots:].view(torch.int32)
         self.finished.fill_(1)
-        self.g = sampler_buffers(slots, V, P, dev)
+        self.g = sampler_buffers(slots, V, P, dev, logprobs=self.logprobs)
         self.logits = torch.zeros(slots, V, device=dev, dtype=cd)
         self.state = ["idle"] * slots                       # idle -> live (admit) -> done (poll) -> idle (take)
         self.lengths = [0] * slots
@@ -136,7 +138,8 @@ class DecodeSession:
             max_length=g["max_length"][rows], logit_bias=g["bias"][rows], advance=True, out=eng.tok_buf[rows],
             history=g["hist"][rows], eos_id=self.eos, pad_id=self.pad, finished=self.finished[rows],
             length=self.length[rows], unfinished=g["unfinished"] if rows == slice(None) else None,
-            pos=eng.pos32[rows] if eng.fused else None)
+            pos=eng.pos32[rows] if eng.fused else None,
+            logprob_history=g["lp_hist"][rows] if self.logprobs else None)
         if not eng.fused:                                   # the generic step's int64 positions: the same rule
             eng.pos_buf[rows] += (self.finished[rows] == 0).to(torch.int64)
 
@@ -145,8 +148,7 @@ class DecodeSession:
         logits buffer (returned: the capture keeps it); launched directly, the
         output is copied into self.logits."""
         eng = self.eng
-        stepfn = eng._step_rows if eng.fused else eng._step
-        lg = stepfn(eng.tok_buf, eng.pos_buf, eng.states)[:, 0]
+        lg = eng.step_fn(self.logprobs)(eng.tok_buf, eng.pos_buf, eng.states)[:, 0]
         if not self.use_graph:
             self.logits.copy_(lg)
             lg = self.logits
@@ -324,17 +326,23 @@ class DecodeSession:
         return [s for s in range(n) if self.state[s] == "done"]
 
     @torch.no_grad()
-    def take(self, slot):
-        """The finished request's tokens, (length,) int64, and the slot idle again."""
+    def take(self, slot, return_logprobs=False):
+        """The finished request's tokens, (length,) int64, and the slot idle
+        again.  return_logprobs, on a session opened with logprobs: (tokens,
+        logprobs (length,) fp32), the log-probability recorded beside every
+        token (DecodeEngine.generate's return_logprobs has the definition)."""
         self._check_slot(slot)
+        if return_logprobs and not self.logprobs:
+            raise ValueError("take: return_logprobs needs a session opened with logprobs=True")
         if self.state[slot] == "live":
             self.poll()
         if self.state[slot] != "done":
             raise RuntimeError(f"take: slot {slot} holds no finished request")
         toks = self.g["hist"][slot, :self.lengths[slot]].clone()
+        lps = self.g["lp_hist"][slot, :self.lengths[slot]].clone() if return_logprobs else None
         self._make_idle(slot)
         self.state[slot] = "idle"
-        return toks
+        return (toks, lps) if return_logprobs else toks
 
 
 def _keys(req):
@@ -344,21 +352,24 @@ def _keys(req):
 
 @torch.no_grad()
 def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                      repetition_window=64):
+                      repetition_window=64, return_logprobs=False):
     """A queue of requests (dicts of DecodeSession.admit's arguments) through
     one session of `slots` rows by the policy of plan_slots.  Returns the
     token tensors in request order, the slot each request ran in and the
-    number of replays made.  With eos_id a row may end before its cap: the
+    number of replays made; with return_logprobs also, last, the requests'
+    log-probability tensors in the same order.  With eos_id a row may end before its cap: the
     loop polls, so the slots then differ from plan_slots' (cap-only) answer;
     no token does."""
     requests = list(requests)
     if int(check_every) < 1:
         raise ValueError("generate_requests: check_every must be >= 1")
     if not requests:
-        return [], [], 0
+        return ([], [], 0, []) if return_logprobs else ([], [], 0)
     if max_keys is None:
         max_keys = max(_keys(r) for r in requests)
-    ses = model.open_session(slots, max_keys, eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window)
+    ses = model.open_session(slots, max_keys, eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
+                             logprobs=bool(return_logprobs))
+    lps = [None] * len(requests)
     out, where = [None] * len(requests), [None] * len(requests)
     left, who = [None] * ses.slots, [None] * ses.slots      # plan_slots' bookkeeping, with the request's index
     nxt = 0
@@ -378,6 +389,11 @@ def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, 
         if n == 0 and not done:
             raise RuntimeError("generate_requests: a request passed its cap without finishing")
         for s in done:
-            out[who[s]] = ses.take(s)
+            if return_logprobs:
+                out[who[s]], lps[who[s]] = ses.take(s, return_logprobs=True)
+            else:
+                out[who[s]] = ses.take(s)
             left[s] = who[s] = None
+    if return_logprobs:
+        return out, where, ses.replays, lps
     return out, where, ses.replays

@@ -26,7 +26,15 @@ max_keys 5248; 1, 8 and 32 slots) and at C4's (max_keys 1024, 32 slots), (p)
 with the parent's routing (DecodeEngine.OPTIONS["split_keys"] off), (s) on the
 split-key kernel with every request at max_keys, (r) on it with request key
 counts uniform in [600, max_keys]; three interleaved repeats.
-python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys] [--out FILE]"""
+--logprobs runs the token log-probability leg instead (vocabulary 10 and 1024,
+top_k=50 / top_p=0.9, penalty 1.3 over a window of 64 on the per-row paths):
+generate() on the scalar path, generate() on the per-row path and a session's
+run(n) with every slot live, each with the feature off and on, three
+interleaved repeats in one process.  With AB_PKG naming another commit's
+package directory (its mamba_decoder.py, mtts/ and libmtts.so) that package
+is timed instead; one that does not know the feature runs the "off" cases
+only, which are the same launches in both.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys | --logprobs] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -36,6 +44,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "mamba-tts-proj
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+
+if os.environ.get("AB_PKG"):    # another commit's package, ahead of this tree's (bench.py has put that first)
+    sys.path.insert(0, os.path.abspath(os.environ["AB_PKG"]))
 
 
 def torch_draw(logits, temperature, top_k, top_p):
@@ -296,6 +307,67 @@ def long_keys_leg(n, dev, lines):
             torch.cuda.empty_cache()
 
 
+def logprobs_leg(n, dev, lines):
+    import inspect
+
+    import mamba_decoder
+    B = 32
+    has = "return_logprobs" in inspect.signature(mamba_decoder.MambaTTSDecoder.generate).parameters
+    lines.append(f"token log-probabilities, C4 (12L d=1024 B=32 bf16), {n} steps, top_k=50 top_p=0.9, us per token "
+                 "(three interleaved repeats in one process, min first; spread = max - min); package "
+                 + os.path.relpath(os.path.dirname(mamba_decoder.__file__), os.path.join(os.path.dirname(__file__), ".."))
+                 + ("" if has else " (no log-probabilities: off cases only)"))
+    for vocab in (10, 1024):
+        c = dict(bench.C2)
+        c["B"] = B
+        torch.manual_seed(0)
+        m = mamba_decoder.MambaTTSDecoder(vocab, d_model=c["d_model"], n_layers=c["n_layers"], n_heads=c["n_heads"],
+                                          d_ff=c["d_ff"], d_style=c["d_style"]).to(dev).eval()
+        m.compute_dtype = torch.bfloat16
+        _, text, z, mask = bench.make_batch(c, dev, 7)
+        kw = dict(top_k=50, top_p=0.9, text_mask=mask, seed=1)
+        rows = dict(temperature=[1.0] * B, repetition_penalty=1.3, repetition_window=64)
+        sessions = {False: m.open_session(B, text.shape[1], repetition_window=64)}
+        if has:
+            sessions[True] = m.open_session(B, text.shape[1], repetition_window=64, logprobs=True)
+
+        def gen(extra, on):
+            flag = dict(return_logprobs=True) if on else {}
+            return timed(lambda: m.generate(text, z, n, **kw, **extra, **flag))
+
+        def session(on):
+            ses = sessions[on]
+            for r in range(B):
+                ses.admit(r, text[r], z[r], text_mask=mask[r], max_new_tokens=n, temperature=1.0, top_k=50,
+                          top_p=0.9, seed=r + 1, repetition_penalty=1.3)
+            t = timed(lambda: ses.run(n))
+            for r in ses.poll():
+                ses.take(r)
+            return t
+
+        cases = [("generate, scalar path", lambda on: gen(dict(temperature=1.0), on)),
+                 ("generate, per-row path, penalty 1.3", lambda on: gen(rows, on)),
+                 ("session, penalty 1.3", session)]
+        cases = [(name + (", logprobs" if on else ""), f, on) for name, f in cases for on in ((False, True) if has
+                                                                                            else (False,))]
+        for _, f, on in cases:
+            f(on)                                          # capture / warm up
+        res = [[] for _ in cases]
+        for _ in range(3):
+            for r, (_, f, on) in zip(res, cases):
+                r.append(f(on) * 1e3 / n)
+        for i, ((name, _, on), r) in enumerate(zip(cases, res)):
+            against = f"  on - off {min(r) - min(res[i - 1]):+.1f}" if on else ""
+            lines.append(f"vocab {vocab:5d} {name:46s} {min(r):7.1f} (" + " ".join(f"{v:.1f}" for v in r)
+                         + f")  spread {max(r) - min(r):.1f}" + against)
+            print(lines[-1], flush=True)
+        lines.append(f"vocab {vocab:5d} graphs captured: generate {len(m._engine.gen_graphs)}, sessions "
+                     + " ".join(str(s.captures) for s in sessions.values()))
+        print(lines[-1], flush=True)
+        del sessions
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=512)
@@ -304,15 +376,17 @@ def main():
     ap.add_argument("--session", action="store_true", help="run the continuous-batching leg instead")
     ap.add_argument("--long-keys", action="store_true", help="run the long-conditioning decode leg instead "
                     "(profiles/decode_long_keys.txt: --steps 256)")
+    ap.add_argument("--logprobs", action="store_true", help="run the token log-probability leg instead "
+                    "(profiles/sample_logprobs_ab.txt)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged or args.rows or args.session or args.long_keys:
+    if args.ragged or args.rows or args.session or args.long_keys or args.logprobs:
         lines = []
         (ragged_leg if args.ragged else rows_leg if args.rows else session_leg if args.session
-         else long_keys_leg)(n, dev, lines)
+         else long_keys_leg if args.long_keys else logprobs_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
