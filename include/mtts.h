@@ -415,6 +415,25 @@ typedef struct {
 int64_t mtts_attention_decode_split_workspace(int batch, int heads, int head_dim, int kv_len);
 int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* a, void* stream);
 
+/* The same for query rows that share K/V rows (n samples of one request).
+ * s as above, except that k, v, key_padding_mask and s.kv_lens have kv_batch
+ * rows: query row b reads K/V row kv_rows[b] and attends to its first
+ * min(s.kv_lens[kv_rows[b]], kv_len) keys.  q, out / out_packed, lse and the
+ * workspace stay per query row (mtts_attention_decode_split_workspace(batch,
+ * ...)).  kv_rows may hold any values: two rows share exactly when their
+ * values are equal, and a value outside [0, kv_batch) gives the row no keys
+ * (NaN, lse -inf; nothing of k / v / mask is read for it).  The first row of
+ * each class loads every chunk of its K/V row once and runs the pass for
+ * each row of the class, so every row's result is the bits
+ * mtts_attention_decode_split gives it on its own copy of the K/V row. */
+typedef struct {
+  MttsAttnDecodeSplitArgs s;
+  const int32_t* kv_rows;    /* (batch) int32 in device memory */
+  int kv_batch;              /* R: rows of k / v / key_padding_mask / s.kv_lens */
+} MttsAttnDecodeSplitSharedArgs;
+
+int mtts_attention_decode_split_shared(const MttsAttnDecodeSplitSharedArgs* a, void* stream);
+
 /* Backward: dout -> dq, dk, dv (same dtype as q).  f.out / f.lse must hold
  * the forward's results.  Deterministic (no atomics). */
 typedef struct {

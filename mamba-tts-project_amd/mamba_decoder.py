@@ -9,7 +9,10 @@
   (reference mamba_decoder.py:50-91).  The two "+res then LN" pairs run as
   one fused HIP kernel (residual add + LayerNorm [+ FiLM]).
 - `MambaTTSDecoder(...)`: embeddings, layer stack, `forward` (teacher forced)
-  and `decode_step` (one AR step with per-layer states kept in HBM).
+  and `decode_step` (one AR step with per-layer states kept in HBM);
+  `generate`, `open_session` / `generate_requests` (continuous batching;
+  `admit_samples` and `share_keys` for n samples of one request that share
+  one K/V projection, one prefill and one copy of the keys).
 
 Reference quirks reproduced on purpose:
   * key_padding_mask = ~text_mask (True in text_mask = attend);
@@ -409,7 +412,8 @@ class MambaTTSDecoder(nn.Module):
                                      check_every=check_every, repetition_penalty=repetition_penalty,
                                      repetition_window=repetition_window, return_logprobs=return_logprobs)
 
-    def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, logprobs=False):
+    def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, logprobs=False,
+                     share_keys=False):
         """A decode session for continuous batching (mtts/session.py
         DecodeSession): `slots` rows over static per-slot buffers, conditioning
         of up to `max_keys` keys per request, one captured graph of step +
@@ -418,25 +422,38 @@ class MambaTTSDecoder(nn.Module):
         slots and take(slot) returns a finished request's tokens and frees
         the slot.  logprobs=True (decided here, with the capture): the session
         records every token's log-probability as generate(return_logprobs=True)
-        does, and take(slot, return_logprobs=True) returns them.  The session
-        owns its buffers and its graph: generate() and decode_step before,
+        does, and take(slot, return_logprobs=True) returns them.
+        admit_samples(slots, ...) puts n samples of one request into n idle
+        slots for one K/V projection and one prefill; member j runs on the
+        seed row_seeds(seed, n)[j] and gives the tokens admit() with that
+        seed gives.  share_keys=True (decided here too): the samples of a
+        request also share ONE copy of its conditioning K/V, which the
+        split-key attention loads once per step for the whole group
+        (mtts_attention_decode_split_shared) with bit-identical results; the
+        slot that holds it stays reserved ("lent") until every member has
+        been taken.  It needs the split-key routing: ValueError when
+        max_keys is inside the single-pass range or split_keys is off.  The
+        session owns its buffers and its graph: generate() and decode_step before,
         during and after it behave as without one."""
         if not self.decode_mode:
             raise RuntimeError("open_session runs on the decode engine: set decode_mode to 'graph' or 'eager'")
         from mtts.session import DecodeSession
         return DecodeSession(self, slots, max_keys, eos_id=eos_id, pad_id=pad_id,
                              repetition_window=repetition_window, use_graph=self.decode_mode == "graph",
-                             logprobs=logprobs)
+                             logprobs=logprobs, share_keys=share_keys)
 
     def generate_requests(self, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                          repetition_window=64, return_logprobs=False):
+                          repetition_window=64, return_logprobs=False, share_keys=False):
         """A queue of requests through one session of `slots` rows, refilled
         as rows finish (mtts/session.py generate_requests, by the policy of
-        mtts.session.plan_slots).  `requests`: dicts of admit's arguments.
+        mtts.session.plan_slots).  `requests`: dicts of admit's arguments; one
+        that carries samples=n is n samples of that request (admit_samples),
+        admitted once n slots are idle, and its entries in the returned lists
+        are lists of n.  share_keys: open the session with it.
         Returns (token tensors in request order, the slot of every request,
         the number of replays made); with return_logprobs a fourth element,
         the requests' log-probability tensors."""
         from mtts.session import generate_requests
         return generate_requests(self, requests, slots=slots, max_keys=max_keys, check_every=check_every,
                                  eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
-                                 return_logprobs=return_logprobs)
+                                 return_logprobs=return_logprobs, share_keys=share_keys)

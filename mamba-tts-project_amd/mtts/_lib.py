@@ -165,6 +165,10 @@ class AttnDecodeSplitArgs(C.Structure):
     _fields_ = [("f", AttnFwdArgs), ("kv_lens", vp), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class AttnDecodeSplitSharedArgs(C.Structure):
+    _fields_ = [("s", AttnDecodeSplitArgs), ("kv_rows", vp), ("kv_batch", i32)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("f", AttnFwdArgs), ("dout", vp), ("do_bs", i64), ("do_ls", i64),
                 ("dq", vp), ("dq_bs", i64), ("dq_ls", i64), ("dk", vp), ("dk_bs", i64), ("dk_ls", i64),
@@ -217,6 +221,7 @@ _SIGS = {
     "mtts_attention_decode_qproj": ([C.POINTER(AttnQProjArgs), vp], i32),
     "mtts_attention_decode_split_workspace": ([i32, i32, i32, i32], i64),
     "mtts_attention_decode_split": ([C.POINTER(AttnDecodeSplitArgs), vp], i32),
+    "mtts_attention_decode_split_shared": ([C.POINTER(AttnDecodeSplitSharedArgs), vp], i32),
     "mtts_attention_bwd_workspace": ([i32, i32, i32, i32, i32, i32], i64),
     "mtts_attention_bwd": ([C.POINTER(AttnBwdArgs), vp], i32),
     "mtts_adam_chunks": ([i64], i64),
@@ -258,7 +263,8 @@ def lib():
                           ("mtts_sample_tokens_slots", "decode sessions"),
                           ("mtts_gemm_grouped_rounds", "round-filling weight gradients"),
                           ("mtts_attention_decode_split", "long-conditioning decode"),
-                          ("mtts_sample_tokens_slots_lp", "token log-probabilities")):
+                          ("mtts_sample_tokens_slots_lp", "token log-probabilities"),
+                          ("mtts_attention_decode_split_shared", "shared-key samples")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "

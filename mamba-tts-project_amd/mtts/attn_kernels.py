@@ -63,16 +63,20 @@ def _mask_u8(kpm, B, S):
     return kpm.view(torch.uint8)
 
 
-def _decode_args(who, q, k, v, n_heads, kpm, want_out, want_packed):
+def _decode_args(who, q, k, v, n_heads, kpm, want_out, want_packed, kv_batch=None):
     """The front end of the single-query calls: AttnFwdArgs for q (B, d)
     against k / v (B, S, d) channel-last or HEAD-MAJOR (B, H, S, hd)
     contiguous (one contiguous K and V block per (batch, head): kv_hs), the
     mask as bytes, and the outputs asked for.  Returns (args, out (B, 1, d) or
     None, PackedAct or None, keep); `keep` holds the aligned copies the
     pointers in args may refer to and must live until the launch.  `who`
-    names the caller in the errors."""
+    names the caller in the errors.  kv_batch: the rows of k / v / kpm when
+    they are not q's (the shared-key call)."""
     from .ops import PackedAct
     B, d = q.shape
+    R = B if kv_batch is None else kv_batch
+    if k.shape[0] != R or v.shape[0] != R:
+        raise ValueError(f"{who}: k / v must have {R} rows")
     q3 = q[:, None]
     if not _aligned(q3):
         q3 = q3.contiguous()
@@ -83,12 +87,12 @@ def _decode_args(who, q, k, v, n_heads, kpm, want_out, want_packed):
         H, S, hd = k.shape[1:]
         if H != n_heads or H * hd != d or k.shape != v.shape or not (k.is_contiguous() and v.is_contiguous()):
             raise ValueError(f"{who}: head-major k / v must be contiguous (B, H, S, hd)")
-        m = _mask_u8(kpm, B, S)
-        a = _fwd_args(q3, k.view(B, H * S, hd), v.view(B, H * S, hd), n_heads, m, o3, None)
+        m = _mask_u8(kpm, R, S)
+        a = _fwd_args(q3, k.view(R, H * S, hd), v.view(R, H * S, hd), n_heads, m, o3, None)
         a.kv_len, a.k_ls, a.v_ls, a.kv_hs = S, hd, hd, S * hd
     else:
         k, v = _prep(k), _prep(v)
-        m = _mask_u8(kpm, B, k.shape[1])
+        m = _mask_u8(kpm, R, k.shape[1])
         a = _fwd_args(q3, k, v, n_heads, m, o3, None)
     a.out = 0 if out is None else out.data_ptr()
     a.out_packed = None if yp is None else yp.data.data_ptr()
@@ -163,7 +167,8 @@ def decode_split_workspace(B, n_heads, hd, S):
     return max(int(L.lib().mtts_attention_decode_split_workspace(B, n_heads, hd, S)), 4)
 
 
-def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=False, want_lse=False, workspace=None):
+def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=False, want_lse=False, workspace=None,
+                           kv_rows=None):
     """Single-query attention over a long key side (mtts_attention_decode_split:
     one workgroup per (batch, head, chunk of decode_split_chunk(hd) keys), then
     a merge in chunk order).  q (B, d); k / v (B, S, d) channel-last or
@@ -173,7 +178,14 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     activation image (ops.PackedAct; bf16, B <= 32) when `packed`; with
     want_lse also the (B, H) fp32 log-sum-exp.  workspace: a uint8 device
     tensor of decode_split_workspace(B, H, hd, S) bytes to keep the partials
-    in (the decode engine holds one per context); None allocates one."""
+    in (the decode engine holds one per context); None allocates one.
+    kv_rows (B,) int32 on the device (mtts_attention_decode_split_shared):
+    k / v / kpm / kv_lens then have R rows of their own, query row b reads
+    K/V row kv_rows[b] with that row's mask and count, and rows with equal
+    values share one load of every chunk; each row's result is the bits the
+    call without kv_rows gives on k[kv_rows], v[kv_rows], ...  A value
+    outside [0, R) gives the row no keys (NaN, lse -inf).  None: today's
+    symbol, k / v per query row."""
     for t in (q, k, v):
         if not t.is_cuda:
             raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
@@ -185,17 +197,25 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     if not (q.dtype == k.dtype == v.dtype):
         raise TypeError("q, k, v must share a dtype")
     hd = d // n_heads
+    R = B
+    if kv_rows is not None:
+        if kv_rows.dtype != torch.int32 or tuple(kv_rows.shape) != (B,) or not kv_rows.is_cuda \
+                or not kv_rows.is_contiguous():
+            raise ValueError(f"attention_decode_split: kv_rows must be ({B},) int32 on the device")
+        R = k.shape[0]
+        if R < 1:
+            raise ValueError("attention_decode_split: kv_rows needs at least one K/V row")
     a, out, yp, keep = _decode_args("attention_decode_split", q, k, v, n_heads, kpm, want_out=not packed,
-                                    want_packed=packed)
+                                    want_packed=packed, kv_batch=R)
     S = a.kv_len
     if S < 1:
         raise ValueError("attention_decode_split: the key side is empty")
     lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
     a.lse = L.ptr(lse)
     if kv_lens is not None:
-        if kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,) or not kv_lens.is_cuda \
+        if kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (R,) or not kv_lens.is_cuda \
                 or not kv_lens.is_contiguous():
-            raise ValueError(f"attention_decode_split: kv_lens must be ({B},) int32 on the device")
+            raise ValueError(f"attention_decode_split: kv_lens must be ({R},) int32 on the device")
     sa = L.AttnDecodeSplitArgs()
     sa.f = a
     sa.kv_lens = L.ptr(kv_lens)
@@ -206,7 +226,12 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     elif ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
         raise ValueError(f"attention_decode_split: workspace must be >= {nbytes} contiguous uint8 bytes on the device")
     sa.workspace, sa.workspace_bytes = ws.data_ptr(), ws.numel()
-    L.call("mtts_attention_decode_split", sa)
+    if kv_rows is None:
+        L.call("mtts_attention_decode_split", sa)
+    else:
+        sh = L.AttnDecodeSplitSharedArgs()
+        sh.s, sh.kv_rows, sh.kv_batch = sa, kv_rows.data_ptr(), R
+        L.call("mtts_attention_decode_split_shared", sh)
     res = yp if packed else out[:, 0]
     return (res, lse) if want_lse else res
 

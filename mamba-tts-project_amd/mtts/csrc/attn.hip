@@ -2008,6 +2008,211 @@ __global__ __launch_bounds__(HD < 64 ? 64 : HD) void attn_decode_merge_kernel(Mt
   decode_store_row<T, HD>(a, b, hh, t, M, L, o);   // n = 0: no chunk, L = 0
 }
 
+// ---------------------------------------------------------------------------
+// The split-key kernel for query rows that share K/V rows (n samples of one
+// request: same keys, values, mask and count, only q differs).  kv_rows[b] is
+// the K/V row of query row b, K, V, the mask and kv_lens have kv_batch rows; a
+// value outside [0, kv_batch) gives the row no keys.  The rows with one value
+// form a class; its first row's workgroup (b, h, c) is the leader: it loads
+// chunk c of the class's K/V row once (decode_load_keys) and runs
+// decode_pass_math, the arithmetic of decode_single_pass, for every row of
+// the class in row order, each with its own q into its own workspace slot.
+// The other rows' workgroups return at once.  Every workgroup finds its role
+// from kv_rows itself (one read of at most batch entries): no atomics, no hand-off,
+// no group list.  A row's partials, and so its result, are the bits
+// attn_decode_split_kernel gives it on its own copy of the keys.
+// ---------------------------------------------------------------------------
+
+// decode_single_pass in two halves, the loads and the arithmetic, for the
+// kernel below, which runs the arithmetic once per query row on one load of
+// the keys.  The statements are decode_single_pass's, one for one: a change
+// to either goes into both (tests/test_gpu_attention_shared.py holds the two
+// to equal bits).  They are a body of their own, not what decode_single_pass
+// is composed of, because composing it moved the register counts of
+// attn_decode1_kernel and attn_decode_split_kernel
+// (profiles/decode_shared_resources.txt).
+//
+// A chunk's K and V as the loads leave them: fp32 as 8 floats per key, bf16
+// as 4 packed words per key (64 registers for the chunk where the converted
+// values take 128; unpack8 converts at each use, to the values ld8 gives).
+template <typename T>
+struct KeyRegs {
+  float k[kDecodeU][8], v[kDecodeU][8];
+};
+template <>
+struct KeyRegs<bf16_t> {
+  uint32_t k[kDecodeU][4], v[kDecodeU][4];
+};
+__device__ __forceinline__ void ld_raw(const float* p, float (&r)[8]) { ld8(p, r); }
+__device__ __forceinline__ void ld_raw(const bf16_t* p, uint32_t (&r)[4]) {
+  const uint4 x = *reinterpret_cast<const uint4*>(p);
+  r[0] = x.x, r[1] = x.y, r[2] = x.z, r[3] = x.w;
+}
+__device__ __forceinline__ void unpack8(float (&r)[8], float (&x)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = r[e];
+}
+// (the empty asm makes the packed words opaque where they are used, so that the conversion is neither hoisted out
+// of the member loop nor done for the whole chunk at once: the chunk stays 64 registers between uses)
+__device__ __forceinline__ void unpack8(uint32_t (&r)[4], float (&x)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    asm volatile("" : "+v"(r[i]));
+    x[2 * i] = __uint_as_float(r[i] << 16), x[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
+  }
+}
+
+// decode_load_keys: K, V and the "counts" flag of keys k0 + g + u * NG of
+// K/V row (b, hh), all loads before any arithmetic.
+template <typename T, int HD>
+__device__ __forceinline__ void decode_load_keys(const MttsAttnFwdArgs& a, int b, int hh, int k0, int n, KeyRegs<T>& r,
+                                                 bool (&ok)[kDecodeU]) {
+  constexpr int G = HD / 8, NG = 256 / G, U = kDecodeU;
+  const int g = threadIdx.x / G, gl = threadIdx.x % G, d0 = gl * 8;
+  const int64_t hs = a.kv_hs ? a.kv_hs : HD;
+  const T* kb = (const T*)a.k + b * a.k_bs + hh * hs + d0;
+  const T* vb = (const T*)a.v + b * a.v_bs + hh * hs + d0;
+  const uint8_t* mb = a.key_padding_mask ? a.key_padding_mask + b * a.mask_bs : (const uint8_t*)a.q;
+  const uint32_t mmask = a.key_padding_mask ? 0xffu : 0u;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = k0 + g + u * NG;
+    const int jj = j < n ? j : k0;   // k0 < n: a key of the row
+    ld_raw(kb + (int64_t)jj * a.k_ls, r.k[u]);
+    ld_raw(vb + (int64_t)jj * a.v_ls, r.v[u]);
+    ok[u] = j < n && ((uint32_t)mb[a.key_padding_mask ? jj : 0] & mmask) == 0;
+  }
+}
+
+// decode_pass_math: the softmax and P.V of one query (the thread's 8 values
+// in q) over the keys decode_load_keys left in registers (kx[u][e] and
+// vx[u][e] of decode_single_pass are unpack8 of r.k[u] and r.v[u]).  Ends on reads of
+// its LDS words that the next call's first barrier orders before that call's
+// writes of them, so calls may follow each other without a barrier between.
+template <typename T, int HD>
+__device__ __forceinline__ void decode_pass_math(float scale, const float (&q)[8], KeyRegs<T>& r,
+                                                 const bool (&ok)[kDecodeU], float& M, float& L, float& o) {
+  constexpr int G = HD / 8, U = kDecodeU;
+  __shared__ float swm[4], swl[4], sacc[4][HD];
+  const int gl = threadIdx.x % G, d0 = gl * 8, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const float c = scale * kLog2e;
+  float sc[U], m = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float sv = 0.f, kx[8];
+    unpack8(r.k[u], kx);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sv = fmaf(q[e], kx[e], sv);
+    sv = group_sum<G>(sv, lane);
+    sc[u] = ok[u] ? sv * c : -INFINITY;
+    m = fmaxf(m, sc[u]);
+  }
+  m = groups_max<G>(m, lane);
+  if ((threadIdx.x & 63) == 0) swm[wave] = m;
+  block_sync();
+  M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
+  float l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float p = ok[u] ? exp2f(sc[u] - M) : 0.f;
+    float vx[8];
+    unpack8(r.v[u], vx);
+    l += p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vx[e], acc[e]);
+  }
+  l = groups_sum<G>(l, lane);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = groups_sum<G>(acc[e], lane);
+  if ((threadIdx.x & 63) < G) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sacc[wave][d0 + e] = acc[e];
+    if (gl == 0) swl[wave] = l;
+  }
+  block_sync();
+  if (threadIdx.x < HD) {
+    L = (swl[0] + swl[1]) + (swl[2] + swl[3]);
+    o = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
+  }
+}
+
+__device__ __forceinline__ int shared_row_keys(const int32_t* kv_lens, const int32_t* kv_rows, int kv_batch, int b,
+                                               int kv_len) {
+  const int r = kv_rows[b];
+  return r < 0 || r >= kv_batch ? 0 : row_keys(kv_lens, r, kv_len);
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void attn_decode_split_shared_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens,
+                                                                        const int32_t* kv_rows, int kv_batch, float* ws,
+                                                                        int nchunk) {
+  const int bh = blockIdx.x, chunk = blockIdx.y, b = bh / a.heads, hh = bh % a.heads;
+  const int n = shared_row_keys(kv_lens, kv_rows, kv_batch, b, a.kv_len), k0 = chunk * split_chunk(HD);
+  if (k0 >= n) return;   // as the split kernel's; also every row whose kv_rows value is out of range (n = 0)
+  // The class's rows as ballots over 64 rows at a time (one coalesced read each, no chain of dependent scalar
+  // reads): every wave reads the same entries, so the answers are uniform over the workgroup.
+  const int kr = kv_rows[b], lane = threadIdx.x & 63, d0 = threadIdx.x % (HD / 8) * 8;
+  for (int base = 0; base < b; base += 64) {
+    const int r = base + lane;
+    if (__ballot(r < b && kv_rows[r] == kr)) return;   // an earlier row leads the class; before any load or barrier
+  }
+  KeyRegs<T> regs;
+  bool ok[kDecodeU];
+  decode_load_keys<T, HD>(a, kr, hh, k0, n, regs, ok);
+  for (int base = b & ~63; base < a.batch; base += 64) {
+    const int rl = base + lane;
+    unsigned long long members = __ballot(rl >= b && rl < a.batch && kv_rows[rl] == kr);
+#pragma unroll 1
+    while (members) {
+      const int r = base + __ffsll(members) - 1;
+      members &= members - 1;
+      float q[8];
+      ld8((const T*)a.q + r * a.q_bs + hh * HD + d0, q);
+      float M, L = 0.f, o = 0.f;
+      decode_pass_math<T, HD>(a.scale, q, regs, ok, M, L, o);
+      if (threadIdx.x < HD) {
+        float* pw = ws + (((int64_t)r * a.heads + hh) * nchunk + chunk) * (HD + 2);
+        if (threadIdx.x == 0) pw[0] = M, pw[1] = L;
+        pw[2 + threadIdx.x] = o;
+      }
+    }
+  }
+}
+
+// attn_decode_merge_kernel with the row's key count taken through kv_rows
+template <typename T, int HD>
+__global__ __launch_bounds__(HD < 64 ? 64 : HD) void attn_decode_merge_shared_kernel(
+    MttsAttnFwdArgs a, const int32_t* kv_lens, const int32_t* kv_rows, int kv_batch, const float* ws, int nchunk) {
+  constexpr int CK = split_chunk(HD);
+  const int bh = blockIdx.x, b = bh / a.heads, hh = bh % a.heads, t = threadIdx.x;
+  if (t >= HD) return;
+  const int n = shared_row_keys(kv_lens, kv_rows, kv_batch, b, a.kv_len), nc = (n + CK - 1) / CK;
+  const float* pw = ws + (int64_t)bh * nchunk * (HD + 2);
+  float M = -INFINITY;
+  for (int i = 0; i < nc; ++i) M = fmaxf(M, pw[(int64_t)i * (HD + 2)]);
+  float L = 0.f, o = 0.f;
+  for (int i = 0; i < nc; ++i) {
+    const float* pi = pw + (int64_t)i * (HD + 2);
+    const float f = pi[0] == -INFINITY ? 0.f : exp2f(pi[0] - M);
+    L += pi[1] * f;
+    o += pi[2 + t] * f;
+  }
+  decode_store_row<T, HD>(a, b, hh, t, M, L, o);
+}
+
+template <typename T, int HD>
+void launch_decode_split_shared(const MttsAttnFwdArgs* a, const int32_t* kv_lens, const int32_t* kv_rows, int kv_batch,
+                                float* ws, hipStream_t st) {
+  constexpr int CK = split_chunk(HD);
+  const int nchunk = (a->kv_len + CK - 1) / CK;
+  const int rows = a->batch * a->heads;
+  hipLaunchKernelGGL((attn_decode_split_shared_kernel<T, HD>), dim3(rows, nchunk), dim3(256), 0, st, *a, kv_lens, kv_rows,
+                     kv_batch, ws, nchunk);
+  hipLaunchKernelGGL((attn_decode_merge_shared_kernel<T, HD>), dim3(rows), dim3(HD < 64 ? 64 : HD), 0, st, *a, kv_lens,
+                     kv_rows, kv_batch, (const float*)ws, nchunk);
+}
+
 template <typename T, int HD>
 void launch_decode_split(const MttsAttnFwdArgs* a, const int32_t* kv_lens, float* ws, hipStream_t st) {
   constexpr int CK = split_chunk(HD);
@@ -2189,23 +2394,35 @@ extern "C" int64_t mtts_attention_decode_split_workspace(int batch, int heads, i
   return decode_split_bytes(batch, heads, head_dim, kv_len);
 }
 
-extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, void* stream) {
-  MTTS_CHECK(s, "attention_decode_split: null args");
+namespace {
+// The checks of the split-key entry points; `who` names the caller.
+int check_decode_split(const MttsAttnDecodeSplitArgs* s, const char* who) {
+  MTTS_CHECK(s, "%s: null args", who);
   const MttsAttnFwdArgs& a = s->f;
-  MTTS_CHECK(a.q_len == 1, "attention_decode_split: q_len %d (the single-query kernels take q_len 1)", a.q_len);
-  MTTS_CHECK(a.out || a.out_packed, "attention_decode_split: null out and out_packed");
-  int rc = check_fwd_either_out(a, "attention_decode_split");
+  MTTS_CHECK(a.q_len == 1, "%s: q_len %d (the single-query kernels take q_len 1)", who, a.q_len);
+  MTTS_CHECK(a.out || a.out_packed, "%s: null out and out_packed", who);
+  int rc = check_fwd_either_out(a, who);
   if (rc) return rc;
-  MTTS_CHECK(a.kv_len >= 1, "attention_decode_split: kv_len %d must be >= 1", a.kv_len);
-  MTTS_CHECK(a.kv_hs % 8 == 0 && a.kv_hs >= 0, "attention_decode_split: kv_hs must be a multiple of 8 elements");
+  MTTS_CHECK(a.kv_len >= 1, "%s: kv_len %d must be >= 1", who, a.kv_len);
+  MTTS_CHECK(a.kv_hs % 8 == 0 && a.kv_hs >= 0, "%s: kv_hs must be a multiple of 8 elements", who);
   MTTS_CHECK(!a.out_packed || (a.dtype == MTTS_BF16 && a.batch <= 32 && (a.heads * a.head_dim) % 32 == 0),
-             "attention_decode_split: out_packed needs bf16, batch <= 32 and heads * head_dim %% 32 == 0 "
-             "(dtype %d, batch %d, d %d)", a.dtype, a.batch, a.heads * a.head_dim);
+             "%s: out_packed needs bf16, batch <= 32 and heads * head_dim %% 32 == 0 "
+             "(dtype %d, batch %d, d %d)", who, a.dtype, a.batch, a.heads * a.head_dim);
   if (a.batch == 0) return MTTS_OK;
   const int64_t need = decode_split_bytes(a.batch, a.heads, a.head_dim, a.kv_len);
   MTTS_CHECK(s->workspace && ((uintptr_t)s->workspace & 3) == 0 && s->workspace_bytes >= need,
-             "attention_decode_split: workspace of %lld bytes, need %lld (4-byte aligned, "
-             "mtts_attention_decode_split_workspace)", (long long)(s->workspace ? s->workspace_bytes : 0), (long long)need);
+             "%s: workspace of %lld bytes, need %lld (4-byte aligned, "
+             "mtts_attention_decode_split_workspace)", who, (long long)(s->workspace ? s->workspace_bytes : 0),
+             (long long)need);
+  return MTTS_OK;
+}
+}  // namespace
+
+extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, void* stream) {
+  int rc = check_decode_split(s, "attention_decode_split");
+  if (rc) return rc;
+  const MttsAttnFwdArgs& a = s->f;
+  if (a.batch == 0) return MTTS_OK;
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)s->workspace;
   with_head_dim(a.head_dim, [&](auto hd) {
@@ -2213,6 +2430,26 @@ extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, voi
     else launch_decode_split<float, hd()>(&a, s->kv_lens, ws, st);
   });
   MTTS_LAUNCH_CHECK("attention_decode_split");
+  return MTTS_OK;
+}
+
+extern "C" int mtts_attention_decode_split_shared(const MttsAttnDecodeSplitSharedArgs* s, void* stream) {
+  MTTS_CHECK(s, "attention_decode_split_shared: null args");
+  int rc = check_decode_split(&s->s, "attention_decode_split_shared");
+  if (rc) return rc;
+  const MttsAttnFwdArgs& a = s->s.f;
+  if (a.batch == 0) return MTTS_OK;
+  MTTS_CHECK(s->kv_rows && ((uintptr_t)s->kv_rows & 3) == 0 && s->kv_batch >= 1,
+             "attention_decode_split_shared: kv_rows (batch int32, device memory) and kv_batch %d >= 1", s->kv_batch);
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)s->s.workspace;
+  with_head_dim(a.head_dim, [&](auto hd) {
+    if (a.dtype == MTTS_BF16)
+      launch_decode_split_shared<bf16_t, hd()>(&a, s->s.kv_lens, s->kv_rows, s->kv_batch, ws, st);
+    else
+      launch_decode_split_shared<float, hd()>(&a, s->s.kv_lens, s->kv_rows, s->kv_batch, ws, st);
+  });
+  MTTS_LAUNCH_CHECK("attention_decode_split_shared");
   return MTTS_OK;
 }
 

@@ -423,7 +423,9 @@ class DecodeEngine:
         layer's entry p, and the one place that picks its kernel.  A long key
         side (_split): the split-key kernel with the context's key counts and
         its workspace, one allocation per context (every layer's partials
-        have the same shape and the layers run in turn on one stream).  Else
+        have the same shape and the layers run in turn on one stream); a
+        context with "kv_rows" (a share_keys session) passes it on, so rows
+        with one value read one K/V row between them.  Else
         a packed step takes the single-pass kernel's packed image, a
         row-major step the single-query kernels of mtts_attention_fwd.  A
         packed step reads the head-major copies of K / V."""
@@ -434,6 +436,9 @@ class DecodeEngine:
             need = decode_split_workspace(q.shape[0], H, hd, S)
             if c["split_ws"] is None or c["split_ws"].numel() < need:
                 c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
+            if c.get("kv_rows") is not None:            # a share_keys session: query row b reads K/V row kv_rows[b]
+                return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed,
+                                              workspace=c["split_ws"], kv_rows=c["kv_rows"])
             return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed, workspace=c["split_ws"])
         if packed:
             return attention_decode_packed(q, k, v, H, c["kpm"])

@@ -16,6 +16,13 @@ control value or seed captures again.  A request's random stream is a function
 of (seed, tokens drawn so far, v) and every kernel of the step is row-wise, so
 its tokens do not depend on its slot, its neighbours or the schedule.
 
+admit_samples() puts n samples of one request into n slots for one K/V
+projection and one prefill; in a session opened with share_keys the group also
+keeps ONE copy of its K/V, in the rows of its first slot, which every member
+reads through the session's (slots,) kv_rows buffer (the split-key attention
+loads it once per step for the whole group, bit-identically), and that slot
+stays reserved ("lent") until every member has been taken.
+
 plan_slots() is the refill policy as a pure host function;
 generate_requests() runs a queue of requests through a session by it.
 """
@@ -25,19 +32,23 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .attn_kernels import key_counts
+from .attn_kernels import decode_split_chunk, key_counts
 from .decode import (DecodeEngine, _check_request, _check_vocab_ids, _check_window, _is_scalar, capture_graph,
                      sampler_buffers)
 from .linear import cast_weight
 
 
-def plan_slots(caps, slots, check_every, prefilled=None):
+def plan_slots(caps, slots, check_every, prefilled=None, samples=None):
     """The refill policy of generate_requests for length caps `caps` (one per
     request, in order) on `slots` rows: admit in order into the lowest free
     slot; replay min(check_every, the largest number of tokens a live row has
     left) times; take what has finished; refill.  prefilled[i] true: request
     i draws its first token at admission (a prompt of more than one token),
-    so it needs one replay less.  Returns (slot of every request, replays)."""
+    so it needs one replay less.  samples[i] = n: request i is n samples of
+    one request (admit_samples); it is admitted once n slots are free, into
+    the n lowest, and until then blocks the requests behind it; its answer is
+    its list of slots (samples[i] None: one slot, an integer, as without
+    `samples`).  Returns (slot of every request, replays)."""
     caps = [int(c) for c in caps]
     slots, check_every = int(slots), int(check_every)
     if slots < 1 or check_every < 1 or any(c < 1 for c in caps):
@@ -45,14 +56,23 @@ def plan_slots(caps, slots, check_every, prefilled=None):
     pre = [False] * len(caps) if prefilled is None else [bool(p) for p in prefilled]
     if len(pre) != len(caps):
         raise ValueError("plan_slots: prefilled must hold one value per request")
+    want = [None] * len(caps) if samples is None else [None if n is None else int(n) for n in samples]
+    if len(want) != len(caps):
+        raise ValueError("plan_slots: samples must hold one value per request")
+    if any(n is not None and not 1 <= n <= slots for n in want):
+        raise ValueError(f"plan_slots: every samples value must be in [1, slots = {slots}]")
     left = [None] * slots                   # tokens the slot's request has still to draw (None: free)
     where, nxt, replays = [], 0, 0
     while nxt < len(caps) or any(v is not None for v in left):
-        for s in range(slots):
-            if left[s] is None and nxt < len(caps):
+        while nxt < len(caps):
+            free = [s for s in range(slots) if left[s] is None]
+            n = 1 if want[nxt] is None else want[nxt]
+            if len(free) < n:               # waits for slots, and so does every request behind it
+                break
+            for s in free[:n]:
                 left[s] = caps[nxt] - (1 if pre[nxt] else 0)
-                where.append(s)
-                nxt += 1
+            where.append(free[0] if want[nxt] is None else free[:n])
+            nxt += 1
         n = min(check_every, max(v for v in left if v is not None))
         replays += n
         left = [None if v is None or v - n <= 0 else v - n for v in left]
@@ -66,7 +86,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def __init__(self, model, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, use_graph=True,
-                 logprobs=False):
+                 logprobs=False, share_keys=False):
         m = self.m = model
         V = m.head.weight.shape[0]
         slots, max_keys = int(slots), int(max_keys)
@@ -81,6 +101,16 @@ class DecodeSession:
         self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), repetition_window
         self.use_graph = bool(use_graph)
         self.logprobs = bool(logprobs)                      # decided here: it selects the one capture
+        self.share_keys = bool(share_keys)                  # so is this: the captured step reads K/V through kv_rows
+        if self.share_keys:                                 # only the split-key kernel takes a K/V row per query row
+            if not DecodeEngine.OPTIONS["split_keys"]:
+                raise ValueError("open_session: share_keys needs the split-key attention and "
+                                 "DecodeEngine.OPTIONS['split_keys'] is off")
+            for l in m.layers:
+                ck = decode_split_chunk(l.cross_attn.embed_dim // l.cross_attn.num_heads)
+                if max_keys <= ck:
+                    raise ValueError(f"open_session: share_keys needs the split-key attention and max_keys = "
+                                     f"{max_keys} is inside the single-pass range (<= {ck} keys at this head dim)")
         self.dev = dev
         d = m.token_embed.weight.shape[1]
         cd = self.cd = m._cd()
@@ -102,6 +132,10 @@ class DecodeSession:
             p["bkv"] = cast_weight(ca.in_proj_bias, cd)[d:]
             for name in ("k", "v", "gamma", "beta"):        # idle rows are zero, before the latch below copies them
                 p[name].zero_()
+        # share_keys: query row r reads the K/V, mask and count of row kv_rows[r]; identity while idle
+        self.kv_rows = torch.arange(slots, dtype=torch.int32, device=dev) if self.share_keys else None
+        if self.share_keys:
+            ctx["kv_rows"] = self.kv_rows
         eng.ctx = ctx
         eng._latch_routing(slots)                           # also makes khm / vhm and the packed FiLM images
         eng._alloc_state(slots, dev)
@@ -118,7 +152,11 @@ class DecodeSession:
         self.finished.fill_(1)
         self.g = sampler_buffers(slots, V, P, dev, logprobs=self.logprobs)
         self.logits = torch.zeros(slots, V, device=dev, dtype=cd)
-        self.state = ["idle"] * slots                       # idle -> live (admit) -> done (poll) -> idle (take)
+        # idle -> live (admit) -> done (poll) -> idle (take); a slot whose K/V rows other slots still read goes
+        # done -> lent (take) -> idle (the last of them taken)
+        self.state = ["idle"] * slots
+        self.holder = list(range(slots))                    # the slot whose K/V rows the slot reads
+        self.borrowers = [set() for _ in range(slots)]      # the other slots that read this slot's K/V rows
         self.lengths = [0] * slots
         self.graph = None
         self.captures = 0
@@ -194,16 +232,53 @@ class DecodeSession:
         shape and a request's K/V does not depend on when or where it was
         admitted.  A prompt of more than one token is prefilled at batch 1
         through the scan path and the first token drawn here."""
-        m, eng, g, dev, V = self.m, self.eng, self.g, self.dev, self.V
         self._check_slot(slot)
+        self._admit("admit", [slot], seed, False, text_hidden, z_style, max_new_tokens, text_mask, ref_hidden, ref_mask,
+                    prompt_tokens, start_token, temperature, top_k, top_p, repetition_penalty, logit_bias)
+
+    @torch.no_grad()
+    def admit_samples(self, slots, text_hidden, z_style, *, max_new_tokens, text_mask=None, ref_hidden=None,
+                      ref_mask=None, prompt_tokens=None, start_token=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                      repetition_penalty=None, logit_bias=None):
+        """n = len(slots) samples of ONE request into n distinct idle slots;
+        the other arguments are admit's.  Every check comes first.  The
+        padded K/V projection of every layer, the FiLM rows and (a prompt of
+        more than one token) the prefill are computed once; member j gets the
+        seed ops.row_seeds(seed, n)[j], its own controls and history, a copy
+        of the prefilled states, and draws its own first token from the
+        shared prefill logits.  Its tokens and log-probabilities are those of
+        admit(slot, ..., seed=row_seeds(seed, n)[j]) alone in any session.
+        In a share_keys session the K/V, mask row and key count are written
+        into slots[0]'s rows only and every member's kv_rows entry names that
+        slot: one load of the keys per step serves the group.  slots[0] then
+        stays reserved until every member has been taken (take()).  In any
+        other session each member's rows get a copy."""
+        if isinstance(slots, (str, bytes)) or not hasattr(slots, "__len__") or len(slots) < 1:
+            raise ValueError("admit_samples: slots must be a list of one or more distinct slots")
+        slots = list(slots)
+        for r in slots:
+            self._check_slot(r)
+        if len(set(slots)) != len(slots):
+            raise ValueError("admit_samples: slots must be a list of one or more distinct slots")
+        self._admit("admit_samples", slots, seed, True, text_hidden, z_style, max_new_tokens, text_mask, ref_hidden,
+                    ref_mask, prompt_tokens, start_token, temperature, top_k, top_p, repetition_penalty, logit_bias)
+
+    def _admit(self, who, rows, seed, expand, text_hidden, z_style, max_new_tokens, text_mask, ref_hidden, ref_mask,
+               prompt_tokens, start_token, temperature, top_k, top_p, repetition_penalty, logit_bias):
+        """One request into the slots `rows` (checked by the caller): what
+        admit and admit_samples share.  expand: member j's seed is
+        row_seeds(seed, n)[j]; else `seed` itself (one row)."""
+        m, eng, g, dev, V = self.m, self.eng, self.g, self.dev, self.V
+        n = len(rows)
         # -- checks: nothing is touched before the last of them ----------------
         for name, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("seed", seed),
                         ("max_new_tokens", max_new_tokens),
                         ("repetition_penalty", 1.0 if repetition_penalty is None else repetition_penalty)):
             if not _is_scalar(v):
                 raise ValueError(f"generate: {name} must be a scalar for one request")
-        ctl = DecodeEngine._row_controls(1, [temperature], [top_k], [top_p], [seed], [max_new_tokens],
-                                         None if repetition_penalty is None else [repetition_penalty], self.window)
+        seeds = ops.row_seeds(int(seed), n) if expand else [seed]
+        ctl = DecodeEngine._row_controls(n, [temperature] * n, [top_k] * n, [top_p] * n, seeds, [max_new_tokens] * n,
+                                         None if repetition_penalty is None else [repetition_penalty] * n, self.window)
         cap = int(ctl["max_length"][0])
         d = m.token_embed.weight.shape[1]
 
@@ -230,62 +305,82 @@ class DecodeSession:
             raise ValueError("admit: the conditioning sequence is empty")
         pt = prompt_tokens[None] if prompt_tokens is not None and prompt_tokens.dim() == 1 else prompt_tokens
         pt, Tp, _ = _check_request(m, 1, cap, pt, start_token, logit_bias, self.pad, self.eos)
-        if self.state[slot] != "idle":
-            raise RuntimeError(f"admit: slot {slot} holds a request that has not been taken")
-        # -- conditioning: [ref ‖ text] padded to max_keys, projected, written in place
+        for r in rows:
+            if self.state[r] == "lent":
+                raise RuntimeError(f"{who}: slot {r} holds the keys of slots {sorted(self.borrowers[r])}, "
+                                   "which have not been taken")
+            if self.state[r] != "idle":
+                raise RuntimeError(f"{who}: slot {r} holds a request that has not been taken")
+        # -- conditioning: [ref ‖ text] padded to max_keys, projected once, written in place: into rows[0] alone in
+        # a share_keys session (every member reads it through kv_rows), into every member's rows otherwise
         cd, K = self.cd, self.max_keys
         th, tm = m._concat_ref(th.to(cd), tm, rh, rm, 1, dev)
         thp = torch.zeros(1, K, d, device=dev, dtype=cd)
         thp[:, :S] = th
         keep = torch.zeros(1, K, dtype=torch.bool, device=dev)
         keep[:, :S] = True if tm is None else tm.to(dev)
-        self.kpm[slot] = ~keep[0]
-        self.kv_lens[slot:slot + 1].copy_(key_counts(keep))  # as generate() derives it from the same mask
-        r = slot
+        kv_to = rows[:1] if self.share_keys else rows
+        counts = key_counts(keep)                           # as generate() derives it from the same mask
+        for r in kv_to:
+            self.kpm[r] = ~keep[0]
+            self.kv_lens[r:r + 1].copy_(counts)
         for l, p in zip(m.layers, eng.ctx["layers"]):
             kv = torch.addmm(p["bkv"], thp.reshape(-1, d), p["Wkv"].t())           # (max_keys, 2d): one shape, always
             lin = l.style_mlp[0]
             gb = torch.tanh(F.linear(z.to(lin.weight.dtype), lin.weight, lin.bias)).to(cd)
-            self._write_cond(p, r, kv[:, :d], kv[:, d:], gb[0, :d], gb[0, d:], l.cross_attn.num_heads)
-        for cs, ss in eng.states:
-            cs[r].zero_()
-            ss[r].zero_()
-        # -- slot state and controls
-        self.length[r:r + 1].zero_()
-        g["draw"][r:r + 1].zero_()
-        for name in ("temperature", "top_k", "top_p", "row_seed", "penalty", "max_length"):
-            g[name][r:r + 1].copy_(ctl[name])
-        if logit_bias is None:
-            g["bias"][r].zero_()
-        else:
-            g["bias"][r].copy_(logit_bias.to(torch.float32).reshape(V))
-        self.finished[r:r + 1].zero_()
-        if Tp > 1:
-            conds = (thp, z, keep, None, None)
-            logits0 = self.pre._prefill(pt.long().to(dev), conds)                   # (1, V); states into self.pre
-            for (cs, ss), (c1, s1) in zip(eng.states, self.pre.states):
-                cs[r].copy_(c1[0])
-                ss[r].copy_(s1[0])
-            eng.pos32[r:r + 1].fill_(Tp - 1)
-            eng.pos_buf[r:r + 1].fill_(Tp - 1)
-            self._sample(logits0, slice(r, r + 1))          # token 0 from the prompt's last logits; pos -> Tp
-        else:
-            eng.tok_buf[r].fill_(int(start_token) if pt is None else 0)
-            if pt is not None:
-                eng.tok_buf[r].copy_(pt[0])
-            eng.pos32[r:r + 1].zero_()
-            eng.pos_buf[r:r + 1].zero_()
-        self.state[slot] = "live"
+            for r in kv_to:
+                self._write_kv(p, r, kv[:, :d], kv[:, d:], l.cross_attn.num_heads)
+            for r in rows:
+                self._write_film(p, r, gb[0, :d], gb[0, d:])
+        if self.share_keys:
+            for r in rows:
+                self.kv_rows[r:r + 1].fill_(rows[0])
+                self.holder[r] = rows[0]
+            self.borrowers[rows[0]] = set(rows[1:])
+        logits0 = None
+        if Tp > 1:                                          # once for the group: states into self.pre
+            logits0 = self.pre._prefill(pt.long().to(dev), (thp, z, keep, None, None))       # (1, V)
+        for j, r in enumerate(rows):
+            for cs, ss in eng.states:
+                cs[r].zero_()
+                ss[r].zero_()
+            # -- slot state and controls
+            self.length[r:r + 1].zero_()
+            g["draw"][r:r + 1].zero_()
+            for name in ("temperature", "top_k", "top_p", "row_seed", "penalty", "max_length"):
+                g[name][r:r + 1].copy_(ctl[name][j:j + 1])
+            if logit_bias is None:
+                g["bias"][r].zero_()
+            else:
+                g["bias"][r].copy_(logit_bias.to(torch.float32).reshape(V))
+            self.finished[r:r + 1].zero_()
+            if Tp > 1:
+                for (cs, ss), (c1, s1) in zip(eng.states, self.pre.states):
+                    cs[r].copy_(c1[0])
+                    ss[r].copy_(s1[0])
+                eng.pos32[r:r + 1].fill_(Tp - 1)
+                eng.pos_buf[r:r + 1].fill_(Tp - 1)
+                self._sample(logits0, slice(r, r + 1))      # token 0 from the prompt's last logits; pos -> Tp
+            else:
+                eng.tok_buf[r].fill_(int(start_token) if pt is None else 0)
+                if pt is not None:
+                    eng.tok_buf[r].copy_(pt[0])
+                eng.pos32[r:r + 1].zero_()
+                eng.pos_buf[r:r + 1].zero_()
+            self.state[r] = "live"
 
-    def _write_cond(self, p, r, k, v, gamma, beta, H):
-        """Row r of one layer's K / V (and head-major copies) and FiLM rows
-        (and packed images), in place.  k, v (max_keys, d); gamma, beta (d,)."""
+    def _write_kv(self, p, r, k, v, H):
+        """Row r of one layer's K / V (and head-major copies), in place.  k, v (max_keys, d)."""
         K, d = k.shape
         p["k"][r].copy_(k)
         p["v"][r].copy_(v)
         if "khm" in p:
             p["khm"][r].copy_(k.reshape(K, H, d // H).permute(1, 0, 2))
             p["vhm"][r].copy_(v.reshape(K, H, d // H).permute(1, 0, 2))
+
+    def _write_film(self, p, r, gamma, beta):
+        """Row r of one layer's FiLM rows (and packed images), in place.  gamma, beta (d,)."""
+        d = gamma.shape[0]
         p["gamma"][r].copy_(gamma)
         p["beta"][r].copy_(beta)
         if "gamma_p" in p:                                  # PackedAct.pack's layout: [s, half, g, row, q]
@@ -298,14 +393,19 @@ class DecodeSession:
         z = torch.zeros((), device=self.dev, dtype=self.cd)
         for l, p in zip(self.m.layers, eng.ctx["layers"]):
             K, d = p["k"].shape[1:]
-            self._write_cond(p, r, z.expand(K, d), z.expand(K, d), z.expand(d), z.expand(d), l.cross_attn.num_heads)
+            self._write_kv(p, r, z.expand(K, d), z.expand(K, d), l.cross_attn.num_heads)
+            self._write_film(p, r, z.expand(d), z.expand(d))
         self.kpm[r] = True
         self.kpm[r, 0] = False
         self.kv_lens[r:r + 1].fill_(1)
+        if self.kv_rows is not None:                        # a borrower reads its own (idle) rows again
+            self.kv_rows[r:r + 1].fill_(r)
+        self.holder[r] = r
         self.finished[r:r + 1].fill_(1)
         eng.tok_buf[r].fill_(self.pad)
         eng.pos32[r:r + 1].zero_()
         eng.pos_buf[r:r + 1].zero_()
+        self.state[r] = "idle"
 
     def poll(self):
         """The slots whose request has finished and has not been taken: one
@@ -328,7 +428,10 @@ class DecodeSession:
     @torch.no_grad()
     def take(self, slot, return_logprobs=False):
         """The finished request's tokens, (length,) int64, and the slot idle
-        again.  return_logprobs, on a session opened with logprobs: (tokens,
+        again -- except a slot whose K/V rows other members of its
+        admit_samples group still read (a share_keys session): it becomes
+        "lent", admit / admit_samples into it raise RuntimeError, and it goes
+        idle, its rows zeroed, when the last of them is taken.  return_logprobs, on a session opened with logprobs: (tokens,
         logprobs (length,) fp32), the log-probability recorded beside every
         token (DecodeEngine.generate's return_logprobs has the definition)."""
         self._check_slot(slot)
@@ -340,8 +443,15 @@ class DecodeSession:
             raise RuntimeError(f"take: slot {slot} holds no finished request")
         toks = self.g["hist"][slot, :self.lengths[slot]].clone()
         lps = self.g["lp_hist"][slot, :self.lengths[slot]].clone() if return_logprobs else None
-        self._make_idle(slot)
-        self.state[slot] = "idle"
+        h = self.holder[slot]
+        if self.borrowers[slot]:                            # other slots still read this slot's K/V rows: they stay,
+            self.state[slot] = "lent"                       # untouched, until the last of those has been taken
+        else:
+            self._make_idle(slot)
+            if h != slot:
+                self.borrowers[h].discard(slot)
+                if not self.borrowers[h] and self.state[h] == "lent":
+                    self._make_idle(h)
         return (toks, lps) if return_logprobs else toks
 
 
@@ -352,12 +462,19 @@ def _keys(req):
 
 @torch.no_grad()
 def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                      repetition_window=64, return_logprobs=False):
+                      repetition_window=64, return_logprobs=False, share_keys=False):
     """A queue of requests (dicts of DecodeSession.admit's arguments) through
     one session of `slots` rows by the policy of plan_slots.  Returns the
     token tensors in request order, the slot each request ran in and the
     number of replays made; with return_logprobs also, last, the requests'
-    log-probability tensors in the same order.  With eos_id a row may end before its cap: the
+    log-probability tensors in the same order.  A request may carry
+    samples=n: it is n samples of one request (admit_samples with the
+    request's seed), admitted in order once n slots are idle -- the requests
+    behind it wait with it, so the order stays deterministic -- into the n
+    lowest idle slots; its entries in the token list, the slot list and the
+    log-probability list are lists of n.  share_keys opens the session with
+    it (the samples of a request then read one copy of its keys); no token
+    depends on it.  With eos_id a row may end before its cap: the
     loop polls, so the slots then differ from plan_slots' (cap-only) answer;
     no token does."""
     requests = list(requests)
@@ -365,23 +482,36 @@ def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, 
         raise ValueError("generate_requests: check_every must be >= 1")
     if not requests:
         return ([], [], 0, []) if return_logprobs else ([], [], 0)
+    want = [r.get("samples") for r in requests]
+    for n in want:
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= int(slots)):
+            raise ValueError(f"generate_requests: samples must be an integer in [1, slots = {int(slots)}]")
     if max_keys is None:
         max_keys = max(_keys(r) for r in requests)
     ses = model.open_session(slots, max_keys, eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
-                             logprobs=bool(return_logprobs))
-    lps = [None] * len(requests)
-    out, where = [None] * len(requests), [None] * len(requests)
-    left, who = [None] * ses.slots, [None] * ses.slots      # plan_slots' bookkeeping, with the request's index
+                             logprobs=bool(return_logprobs), share_keys=share_keys)
+    lps = [None if n is None else [None] * n for n in want]
+    out, where = [None if n is None else [None] * n for n in want], [None] * len(requests)
+    left, who = [None] * ses.slots, [None] * ses.slots      # plan_slots' bookkeeping, with (request, member)
     nxt = 0
     while nxt < len(requests) or any(v is not None for v in left):
-        for s in range(ses.slots):
-            if left[s] is None and nxt < len(requests):
-                req = requests[nxt]
-                ses.admit(s, **req)
-                pt = req.get("prompt_tokens")
+        while nxt < len(requests):
+            free = [s for s in range(ses.slots) if left[s] is None and ses.state[s] == "idle"]
+            n = 1 if want[nxt] is None else want[nxt]
+            if len(free) < n:
+                break
+            req = requests[nxt]
+            if want[nxt] is None:
+                ses.admit(free[0], **req)
+                where[nxt] = free[0]
+            else:
+                ses.admit_samples(free[:n], **{k: v for k, v in req.items() if k != "samples"})
+                where[nxt] = free[:n]
+            pt = req.get("prompt_tokens")
+            for j, s in enumerate(free[:n]):
                 left[s] = int(req["max_new_tokens"]) - (1 if pt is not None and pt.shape[-1] > 1 else 0)
-                who[s], where[nxt] = nxt, s
-                nxt += 1
+                who[s] = (nxt, None if want[nxt] is None else j)
+            nxt += 1
         n = min(int(check_every), max(v for v in left if v is not None))
         ses.run(n)
         left = [None if v is None else max(v - n, 0) for v in left]
@@ -389,10 +519,12 @@ def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, 
         if n == 0 and not done:
             raise RuntimeError("generate_requests: a request passed its cap without finishing")
         for s in done:
-            if return_logprobs:
-                out[who[s]], lps[who[s]] = ses.take(s, return_logprobs=True)
+            got = ses.take(s, return_logprobs=True) if return_logprobs else (ses.take(s), None)
+            i, j = who[s]
+            if j is None:
+                out[i], lps[i] = got
             else:
-                out[who[s]] = ses.take(s)
+                out[i][j], lps[i][j] = got
             left[s] = who[s] = None
     if return_logprobs:
         return out, where, ses.replays, lps

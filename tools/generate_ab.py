@@ -34,7 +34,16 @@ interleaved repeats in one process.  With AB_PKG naming another commit's
 package directory (its mamba_decoder.py, mtts/ and libmtts.so) that package
 is timed instead; one that does not know the feature runs the "off" cases
 only, which are the same launches in both.
-python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys | --logprobs] [--out FILE]"""
+--shared-keys runs the parallel-samples leg instead (--steps 256): train.py's
+widths (8 layers, d_model 512), max_keys 5248, 32 slots, every slot live and
+every request at max_keys, as 32 x 1, 16 x 2, 8 x 4 and 4 x 8 (groups x
+samples of one request, admit_samples): us per token of a share_keys session
+(one copy of a group's K/V, loaded once per step for the group) against a
+plain session whose members hold copies (what n unrelated requests cost), five
+interleaved repeats in one process, median, min and max; then the wall time of
+one admit_samples of 4 against four admits.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys | --logprobs | --shared-keys]
+                            [--out FILE]"""
 import argparse
 import os
 import sys
@@ -307,6 +316,89 @@ def long_keys_leg(n, dev, lines):
             torch.cuda.empty_cache()
 
 
+def shared_keys_leg(n, dev, lines):
+    """n samples of one request: a share_keys session against a plain one
+    whose members hold copies of the K/V, then the admission itself."""
+    import statistics
+    import time
+
+    import mamba_decoder
+    vocab, slots, max_keys, d, reps = 1024, 32, 5248, 512, 5
+    lines.append(f"parallel samples of one request, train.py widths (8L d=512 8 heads), bf16, vocab {vocab}, max_keys "
+                 f"{max_keys}, {slots} slots, every slot live, every request at max_keys, {n} steps, top_k=50 top_p=0.9, "
+                 f"us per token ({reps} interleaved repeats in one process: median [min max]; spread = max - min).  "
+                 "(c) plain session, every member holds a copy of the K/V; (s) share_keys session, one copy per group")
+    torch.manual_seed(0)
+    m = mamba_decoder.MambaTTSDecoder(vocab, d_ff=2048, d_style=256, n_layers=8, d_model=d, n_heads=8).to(dev).eval()
+    m.compute_dtype = torch.bfloat16
+    g = torch.Generator().manual_seed(5)
+    text = torch.randn(slots, max_keys, d, generator=g).to(dev)
+    z = torch.randn(slots, 256, generator=g).to(dev)
+    ses = {"c": m.open_session(slots, max_keys, repetition_window=64),
+           "s": m.open_session(slots, max_keys, repetition_window=64, share_keys=True)}
+    kw = dict(temperature=1.0, top_k=50, top_p=0.9)
+
+    def fmt(v):
+        return f"{statistics.median(v):8.1f} [{min(v):.1f} {max(v):.1f}]  spread {max(v) - min(v):.1f}"
+
+    def run(leg, per):
+        s = ses[leg]
+        for i in range(slots // per):
+            s.admit_samples(list(range(i * per, (i + 1) * per)), text[i], z[i], max_new_tokens=n, seed=i + 1, **kw)
+        t = timed(lambda: s.run(n))
+        for r in s.poll():
+            s.take(r)
+        assert s.state == ["idle"] * slots
+        return t * 1e3 / n
+
+    for per in (1, 2, 4, 8):
+        for leg in ses:
+            run(leg, per)                                      # warm up
+        res = {leg: [] for leg in ses}
+        for _ in range(reps):
+            for leg in ses:
+                res[leg].append(run(leg, per))
+        diff = statistics.median(res["s"]) - statistics.median(res["c"])
+        lines.append(f"{slots // per:2d} x {per}  (c) copies {fmt(res['c'])}   (s) shared {fmt(res['s'])}   "
+                     f"(s) - (c) {diff:+.1f}")
+        print(lines[-1], flush=True)
+
+    lines.append("admission of 4 samples of one request, wall ms with a synchronize on both sides "
+                 f"({reps} interleaved repeats: median [min max]): four admit()s, admit_samples of 4 into a plain "
+                 "session (copies), admit_samples of 4 into a share_keys session")
+    for prompt in (0, 64):
+        pt = torch.randint(0, vocab, (prompt,), generator=g).to(dev) if prompt else None
+
+        def admission(leg, together):
+            s = ses[leg]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if together:
+                s.admit_samples([0, 1, 2, 3], text[0], z[0], max_new_tokens=2, seed=1, prompt_tokens=pt, **kw)
+            else:
+                for r in range(4):
+                    s.admit(r, text[0], z[0], max_new_tokens=2, seed=r + 1, prompt_tokens=pt, **kw)
+            torch.cuda.synchronize()
+            t = (time.perf_counter() - t0) * 1e3
+            s.run(2)
+            for r in s.poll():
+                s.take(r)
+            return t
+
+        cases = (("four admits", "c", False), ("admit_samples, copies", "c", True), ("admit_samples, shared", "s", True))
+        for _, leg, tog in cases:
+            admission(leg, tog)
+        res = [[] for _ in cases]
+        for _ in range(reps):
+            for r, (_, leg, tog) in zip(res, cases):
+                r.append(admission(leg, tog))
+        lines.append(f"prompt of {prompt:2d} tokens: " + "   ".join(
+            f"{name} {statistics.median(r):.2f} [{min(r):.2f} {max(r):.2f}]" for (name, _, _), r in zip(cases, res)))
+        print(lines[-1], flush=True)
+    lines.append("graphs captured: " + " ".join(str(s.captures) for s in ses.values()))
+    print(lines[-1], flush=True)
+
+
 def logprobs_leg(n, dev, lines):
     import inspect
 
@@ -378,15 +470,17 @@ def main():
                     "(profiles/decode_long_keys.txt: --steps 256)")
     ap.add_argument("--logprobs", action="store_true", help="run the token log-probability leg instead "
                     "(profiles/sample_logprobs_ab.txt)")
+    ap.add_argument("--shared-keys", action="store_true", help="run the parallel-samples leg instead "
+                    "(profiles/shared_keys_ab.txt: --steps 256)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged or args.rows or args.session or args.long_keys or args.logprobs:
+    if args.ragged or args.rows or args.session or args.long_keys or args.logprobs or args.shared_keys:
         lines = []
         (ragged_leg if args.ragged else rows_leg if args.rows else session_leg if args.session
-         else long_keys_leg if args.long_keys else logprobs_leg)(n, dev, lines)
+         else long_keys_leg if args.long_keys else shared_keys_leg if args.shared_keys else logprobs_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
