@@ -434,6 +434,64 @@ typedef struct {
 
 int mtts_attention_decode_split_shared(const MttsAttnDecodeSplitSharedArgs* a, void* stream);
 
+/* Conditioning K / V as OCP FP8 (e4m3fn, the format gfx950 converts in
+ * hardware) with one fp32 scale per (row, head) (csrc/kvq.hip; opt-in,
+ * DecodeEngine.generate / open_session kv_dtype="fp8").
+ * x (rows, kv_len, heads * head_dim) bf16 / fp32, channel-last, unit inner
+ * stride, x_bs / x_ls in elements (x may be a column view of the (.., 2d) K/V
+ * projection; the base and both strides 16-byte aligned).  kv_lens (rows)
+ * int32 in device memory or NULL (= kv_len), clamped to [0, kv_len]: n_r.
+ *   scale[r * scale_bs + h] = amax / 448, amax = max |x| over the head's
+ *     head_dim columns of keys j < n_r (keys a padding mask hides take part);
+ *     amax == 0 gives 1; a NaN or infinity among the counted keys gives NaN
+ *     (and NaN codes for the row's head: the caller's to avoid);
+ *   out[r * out_bs + (h * kv_len + j) * head_dim + c], head-major bytes
+ *     (rows, heads, kv_len, head_dim): e4m3fn(fp32(x) / scale), IEEE fp32
+ *     division, round to nearest even, for j < n_r; 0x00 for n_r <= j < kv_len.
+ * The bits are those of (x.float() / scale).to(torch.float8_e4m3fn).  The max
+ * is exact in any order and nothing else is reduced, so a row's result depends
+ * on the row alone.  out_bs (bytes, multiple of 8) and scale_bs (floats) let
+ * out / scale be row slices of larger buffers: other rows are not touched.
+ * Two launches, (row, head, chunk of 256 keys) workgroups each: amax partials
+ * into the workspace, then scale + convert + transpose. */
+typedef struct {
+  int rows, heads, head_dim, kv_len;
+  int dtype;                 /* MTTS_F32 / MTTS_BF16 of x */
+  int reserved_;
+  int64_t x_bs, x_ls;        /* element strides of x */
+  int64_t out_bs;            /* bytes between rows of out (>= heads * kv_len * head_dim) */
+  int64_t scale_bs;          /* floats between rows of scale (>= heads) */
+  const void* x;
+  const int32_t* kv_lens;    /* may be NULL */
+  uint8_t* out;              /* 8-byte aligned */
+  float* scale;
+  void* workspace;           /* mtts_kv_quantize_fp8_workspace() bytes, 4-byte aligned */
+  int64_t workspace_bytes;
+} MttsKvQuantizeFp8Args;
+
+int64_t mtts_kv_quantize_fp8_workspace(int rows, int heads, int head_dim, int kv_len);
+int mtts_kv_quantize_fp8(const MttsKvQuantizeFp8Args* a, void* stream);
+
+/* mtts_attention_decode_split over such K / V.  s as above with s.f.k / s.f.v
+ * the e4m3fn bytes (strides k_bs / k_ls / v_bs / v_ls / kv_hs in elements =
+ * bytes; pointers and strides 16-byte aligned) and s.f.dtype the dtype of q and
+ * out (bf16 / fp32).  With deq the exact fp32 value of a byte, per (b, h):
+ *   score_j = (q . deq(k_j)) * (scale * log2e * k_scale[b * scale_bs + h]),
+ * p and the chunk partial as mtts_attention_decode_split's, the accumulator
+ * multiplied by v_scale[b * scale_bs + h] once before the partial is written.
+ * Same chunk (16384 / head_dim keys), grid, early return, clamped key index,
+ * merge launch, outputs and workspace as the bf16 kernel: a row's bits depend
+ * on the row alone.  No byte at or past a row's count and no scale of another
+ * row is read. */
+typedef struct {
+  MttsAttnDecodeSplitArgs s;
+  const float* k_scale;      /* (batch, heads) fp32, row stride scale_bs */
+  const float* v_scale;
+  int64_t scale_bs;
+} MttsAttnDecodeSplitFp8Args;
+
+int mtts_attention_decode_split_fp8(const MttsAttnDecodeSplitFp8Args* a, void* stream);
+
 /* Backward: dout -> dq, dk, dv (same dtype as q).  f.out / f.lse must hold
  * the forward's results.  Deterministic (no atomics). */
 typedef struct {

@@ -351,7 +351,7 @@ class MambaTTSDecoder(nn.Module):
     def generate(self, text_hidden, z_style, max_new_tokens, *, prompt_tokens=None, prompt_lengths=None, start_token=0,
                  text_mask=None, ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0,
                  logit_bias=None, eos_id=None, pad_id=0, seed=0, check_every=32, repetition_penalty=None,
-                 repetition_window=64, return_logprobs=False):
+                 repetition_window=64, return_logprobs=False, kv_dtype=None):
         """Generate up to `max_new_tokens` codec tokens on the device
         (mtts/decode.py DecodeEngine.generate): the decode_step loop with the
         draw (temperature, top-k, top-p, reproducible from `seed`) in the HIP
@@ -394,6 +394,13 @@ class MambaTTSDecoder(nn.Module):
         and before top-k / top-p -- independent of the sampling settings, for
         greedy rows too.  Computed in the sampler's launch; no per-token copy.
 
+        kv_dtype="fp8" (None: off): the conditioning K / V are kept as OCP
+        FP8 (e4m3fn) with one fp32 scale per (row, head) and every decode step
+        reads them through the fp8 form of the split-key attention -- half the
+        K/V bytes per token, for key sides past the single-pass range only
+        (ValueError otherwise).  The prompt prefill runs over the unquantised
+        conditioning.  DecodeEngine.generate has the details.
+
         Returns tokens (B, n) int64 with n <= max(max_new_tokens) and lengths (B,)
         int64 (tokens up to and including a row's eos_id); with
         return_logprobs also logprobs (B, n) fp32, 0.0 at and past a row's
@@ -410,10 +417,11 @@ class MambaTTSDecoder(nn.Module):
                                      ref_mask=ref_mask, temperature=temperature, top_k=top_k, top_p=top_p,
                                      logit_bias=logit_bias, eos_id=eos_id, pad_id=pad_id, seed=seed,
                                      check_every=check_every, repetition_penalty=repetition_penalty,
-                                     repetition_window=repetition_window, return_logprobs=return_logprobs)
+                                     repetition_window=repetition_window, return_logprobs=return_logprobs,
+                                     kv_dtype=kv_dtype)
 
     def open_session(self, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, logprobs=False,
-                     share_keys=False):
+                     share_keys=False, kv_dtype=None):
         """A decode session for continuous batching (mtts/session.py
         DecodeSession): `slots` rows over static per-slot buffers, conditioning
         of up to `max_keys` keys per request, one captured graph of step +
@@ -432,7 +440,12 @@ class MambaTTSDecoder(nn.Module):
         (mtts_attention_decode_split_shared) with bit-identical results; the
         slot that holds it stays reserved ("lent") until every member has
         been taken.  It needs the split-key routing: ValueError when
-        max_keys is inside the single-pass range or split_keys is off.  The
+        max_keys is inside the single-pass range or split_keys is off.
+        kv_dtype="fp8" (decided here as well): the session keeps every slot's
+        conditioning K/V as FP8 bytes with a scale per (slot, head), a quarter
+        of the K/V bytes a packed bf16 session holds, and the captured step
+        reads them through the fp8 split-key attention (generate's kv_dtype);
+        same ValueErrors, and not together with share_keys.  The
         session owns its buffers and its graph: generate() and decode_step before,
         during and after it behave as without one."""
         if not self.decode_mode:
@@ -440,20 +453,20 @@ class MambaTTSDecoder(nn.Module):
         from mtts.session import DecodeSession
         return DecodeSession(self, slots, max_keys, eos_id=eos_id, pad_id=pad_id,
                              repetition_window=repetition_window, use_graph=self.decode_mode == "graph",
-                             logprobs=logprobs, share_keys=share_keys)
+                             logprobs=logprobs, share_keys=share_keys, kv_dtype=kv_dtype)
 
     def generate_requests(self, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                          repetition_window=64, return_logprobs=False, share_keys=False):
+                          repetition_window=64, return_logprobs=False, share_keys=False, kv_dtype=None):
         """A queue of requests through one session of `slots` rows, refilled
         as rows finish (mtts/session.py generate_requests, by the policy of
         mtts.session.plan_slots).  `requests`: dicts of admit's arguments; one
         that carries samples=n is n samples of that request (admit_samples),
         admitted once n slots are idle, and its entries in the returned lists
-        are lists of n.  share_keys: open the session with it.
+        are lists of n.  share_keys, kv_dtype: open the session with them.
         Returns (token tensors in request order, the slot of every request,
         the number of replays made); with return_logprobs a fourth element,
         the requests' log-probability tensors."""
         from mtts.session import generate_requests
         return generate_requests(self, requests, slots=slots, max_keys=max_keys, check_every=check_every,
                                  eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
-                                 return_logprobs=return_logprobs, share_keys=share_keys)
+                                 return_logprobs=return_logprobs, share_keys=share_keys, kv_dtype=kv_dtype)

@@ -169,6 +169,16 @@ class AttnDecodeSplitSharedArgs(C.Structure):
     _fields_ = [("s", AttnDecodeSplitArgs), ("kv_rows", vp), ("kv_batch", i32)]
 
 
+class KvQuantizeFp8Args(C.Structure):
+    _fields_ = [("rows", i32), ("heads", i32), ("head_dim", i32), ("kv_len", i32), ("dtype", i32), ("reserved_", i32),
+                ("x_bs", i64), ("x_ls", i64), ("out_bs", i64), ("scale_bs", i64),
+                ("x", vp), ("kv_lens", vp), ("out", vp), ("scale", vp), ("workspace", vp), ("workspace_bytes", i64)]
+
+
+class AttnDecodeSplitFp8Args(C.Structure):
+    _fields_ = [("s", AttnDecodeSplitArgs), ("k_scale", vp), ("v_scale", vp), ("scale_bs", i64)]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("f", AttnFwdArgs), ("dout", vp), ("do_bs", i64), ("do_ls", i64),
                 ("dq", vp), ("dq_bs", i64), ("dq_ls", i64), ("dk", vp), ("dk_bs", i64), ("dk_ls", i64),
@@ -222,6 +232,9 @@ _SIGS = {
     "mtts_attention_decode_split_workspace": ([i32, i32, i32, i32], i64),
     "mtts_attention_decode_split": ([C.POINTER(AttnDecodeSplitArgs), vp], i32),
     "mtts_attention_decode_split_shared": ([C.POINTER(AttnDecodeSplitSharedArgs), vp], i32),
+    "mtts_attention_decode_split_fp8": ([C.POINTER(AttnDecodeSplitFp8Args), vp], i32),
+    "mtts_kv_quantize_fp8_workspace": ([i32, i32, i32, i32], i64),
+    "mtts_kv_quantize_fp8": ([C.POINTER(KvQuantizeFp8Args), vp], i32),
     "mtts_attention_bwd_workspace": ([i32, i32, i32, i32, i32, i32], i64),
     "mtts_attention_bwd": ([C.POINTER(AttnBwdArgs), vp], i32),
     "mtts_adam_chunks": ([i64], i64),
@@ -264,7 +277,8 @@ def lib():
                           ("mtts_gemm_grouped_rounds", "round-filling weight gradients"),
                           ("mtts_attention_decode_split", "long-conditioning decode"),
                           ("mtts_sample_tokens_slots_lp", "token log-probabilities"),
-                          ("mtts_attention_decode_split_shared", "shared-key samples")):
+                          ("mtts_attention_decode_split_shared", "shared-key samples"),
+                          ("mtts_attention_decode_split_fp8", "FP8 conditioning K/V")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "

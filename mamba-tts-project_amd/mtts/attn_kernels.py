@@ -236,6 +236,106 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     return (res, lse) if want_lse else res
 
 
+def _check_kv_lens(who, kv_lens, R):
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (R,) or not kv_lens.is_cuda
+                                or not kv_lens.is_contiguous()):
+        raise ValueError(f"{who}: kv_lens must be ({R},) int32 on the device")
+
+
+def quantize_kv_fp8(x, n_heads, kv_lens=None, out=None, scale_out=None):
+    """K or V of a conditioning sequence as OCP FP8 (e4m3fn) with one fp32
+    scale per (row, head) (mtts_kv_quantize_fp8, csrc/kvq.hip).  x (R, S, d)
+    bf16 / fp32 channel-last with unit inner stride -- a column view of the
+    (R, S, 2d) K/V projection is taken as it is; kv_lens (R,) int32 on the
+    device: row r's first kv_lens[r] keys (clamped to [0, S]) count, None: S.
+    Returns (bytes (R, H, S, hd) torch.uint8, head-major, scale (R, H) fp32):
+    scale = max |x| over the head's counted keys / 448 (1 for an all-zero
+    head), bytes = (x.float() / scale).to(torch.float8_e4m3fn) bit for bit for
+    the counted keys and 0 for the others.  A NaN or infinity among a head's
+    counted keys makes its scale NaN.  out / scale_out: where to write, e.g.
+    one slot's rows of a session's buffers (out[r] contiguous, scale_out[r]
+    contiguous; the rows may be strided); other rows are not touched."""
+    if not x.is_cuda:
+        raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
+    if x.dim() != 3:
+        raise ValueError("quantize_kv_fp8: x must be (R, S, d)")
+    R, S, d = x.shape
+    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
+        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
+    hd = d // n_heads
+    _check_kv_lens("quantize_kv_fp8", kv_lens, R)
+    x = _prep(x)
+    if out is None:
+        out = torch.empty(R, n_heads, S, hd, device=x.device, dtype=torch.uint8)
+    elif (out.dtype != torch.uint8 or tuple(out.shape) != (R, n_heads, S, hd) or not out.is_cuda
+          or (R and not out[0].is_contiguous())):
+        raise ValueError(f"quantize_kv_fp8: out must be ({R}, {n_heads}, {S}, {hd}) uint8 on the device, rows contiguous")
+    if scale_out is None:
+        scale_out = torch.empty(R, n_heads, device=x.device, dtype=torch.float32)
+    elif (scale_out.dtype != torch.float32 or tuple(scale_out.shape) != (R, n_heads) or not scale_out.is_cuda
+          or scale_out.stride(1) != 1):
+        raise ValueError(f"quantize_kv_fp8: scale_out must be ({R}, {n_heads}) fp32 on the device, rows contiguous")
+    a = L.KvQuantizeFp8Args()
+    a.rows, a.heads, a.head_dim, a.kv_len, a.dtype = R, n_heads, hd, S, L.dtype_code(x)
+    a.x_bs, a.x_ls = x.stride(0), x.stride(1)
+    a.out_bs = out.stride(0) if R > 1 else n_heads * S * hd
+    a.scale_bs = scale_out.stride(0) if R > 1 else n_heads
+    a.x, a.kv_lens, a.out, a.scale = x.data_ptr(), L.ptr(kv_lens), out.data_ptr(), scale_out.data_ptr()
+    nbytes = max(int(L.lib().mtts_kv_quantize_fp8_workspace(R, n_heads, hd, S)), 4)
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.call("mtts_kv_quantize_fp8", a)
+    return out, scale_out
+
+
+def attention_decode_split_fp8(q, k8, v8, k_scale, v_scale, n_heads, kpm=None, kv_lens=None, packed=False,
+                               want_lse=False, workspace=None):
+    """attention_decode_split over FP8 K / V (mtts_attention_decode_split_fp8):
+    k8 / v8 (B, H, S, hd) torch.uint8 head-major contiguous and k_scale /
+    v_scale (B, H) fp32, as quantize_kv_fp8 returns them; q (B, d) bf16 or
+    fp32, the dtype of the output.  With K^ = deq(k8) * k_scale and V^ alike,
+    the result is softmax(q K^T / sqrt(hd)) V^ with fp32 accumulation; kpm,
+    kv_lens, packed, want_lse and workspace (decode_split_workspace bytes) as
+    attention_decode_split.  No byte at or past a row's count is read."""
+    for t in (q, k8, v8, k_scale, v_scale):
+        if not t.is_cuda:
+            raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
+    if q.dim() != 2:
+        raise ValueError("attention_decode_split_fp8: q must be (B, d)")
+    B, d = q.shape
+    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
+        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
+    hd = d // n_heads
+    if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or k8.dim() != 4:
+        raise TypeError("attention_decode_split_fp8: k8 / v8 must be (B, H, S, hd) torch.uint8 (e4m3fn bytes)")
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s.dtype != torch.float32 or tuple(s.shape) != (B, n_heads) or not s.is_contiguous():
+            raise ValueError(f"attention_decode_split_fp8: {name} must be ({B}, {n_heads}) fp32, contiguous")
+    a, out, yp, keep = _decode_args("attention_decode_split_fp8", q, k8, v8, n_heads, kpm, want_out=not packed,
+                                    want_packed=packed)
+    S = a.kv_len
+    if S < 1:
+        raise ValueError("attention_decode_split_fp8: the key side is empty")
+    lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
+    a.lse = L.ptr(lse)
+    _check_kv_lens("attention_decode_split_fp8", kv_lens, B)
+    fa = L.AttnDecodeSplitFp8Args()
+    fa.s.f = a
+    fa.s.kv_lens = L.ptr(kv_lens)
+    nbytes = decode_split_workspace(B, n_heads, hd, S)
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
+    elif ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise ValueError(f"attention_decode_split_fp8: workspace must be >= {nbytes} contiguous uint8 bytes on the "
+                         "device")
+    fa.s.workspace, fa.s.workspace_bytes = ws.data_ptr(), ws.numel()
+    fa.k_scale, fa.v_scale, fa.scale_bs = k_scale.data_ptr(), v_scale.data_ptr(), n_heads
+    L.call("mtts_attention_decode_split_fp8", fa)
+    res = yp if packed else out[:, 0]
+    return (res, lse) if want_lse else res
+
+
 def attention_fwd(q, k, v, n_heads, kpm=None, want_lse=False):
     """Returns (out (B, T, d) in q's dtype, lse (B, H, T) fp32 or None)."""
     for t in (q, k, v):

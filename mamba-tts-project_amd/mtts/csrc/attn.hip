@@ -2009,6 +2009,130 @@ __global__ __launch_bounds__(HD < 64 ? 64 : HD) void attn_decode_merge_kernel(Mt
 }
 
 // ---------------------------------------------------------------------------
+// The split-key kernel over FP8 K / V (OCP e4m3fn bytes, one fp32 scale per
+// (row, head); kvq.hip writes them): half the bytes of the bf16 kernel, which
+// at these key counts is what the step waits for.  Same chunk, grid, early
+// return and clamped key index as attn_decode_split_kernel, and the merge
+// launch is that kernel's.  A lane owns 16 dims of a key -- one 16-byte load
+// of K and of V, HD / 16 lanes a key, 4 keys per group instead of 8, so the
+// chunk is unchanged; 8 dims per lane and 8-byte loads measured 829 against
+// 785 us per token at 32 slots of 5248 keys (profiles/kv_fp8_ab.txt).  The
+// loaded K / V stay raw words (4 VGPRs per key and operand instead of 16) and
+// are converted where they are used (v_cvt_pk_f32_fp8: exact).  The scales enter outside the sums: the score is
+// (q . deq(k)) * (scale * log2e * k_scale), the accumulator is multiplied by
+// v_scale once before the partial is written.  T is the dtype of q and out.
+// ---------------------------------------------------------------------------
+typedef float fp8_f32x2 __attribute__((ext_vector_type(2)));
+
+// the 8 e4m3fn bytes of w as fp32, in memory order
+__device__ __forceinline__ void fp8x8_to_f32(uint2 w, float (&v)[8]) {
+  const fp8_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(w.x, true);
+  const fp8_f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8(w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(w.y, true);
+  v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1], v[4] = c[0], v[5] = c[1], v[6] = d[0], v[7] = d[1];
+}
+
+struct Fp8Scales {
+  const float* k;
+  const float* v;
+  int64_t bs;
+};
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void attn_decode_split_fp8_kernel(MttsAttnFwdArgs a, const int32_t* kv_lens,
+                                                                     Fp8Scales sc8, float* ws, int nchunk) {
+  constexpr int LD = 16, W = LD / 8;   // dims per lane (one 16-byte load of K and of V per key), 8-byte words in them
+  constexpr int G = HD / LD, NG = 256 / G, U = split_chunk(HD) / NG;
+  __shared__ float swm[4], swl[4], sacc[4][HD];
+  const int bh = blockIdx.x, chunk = blockIdx.y, b = bh / a.heads, hh = bh % a.heads;
+  const int n = row_keys(kv_lens, b, a.kv_len), k0 = chunk * split_chunk(HD);
+  if (k0 >= n) return;   // uniform over the workgroup; before any load or barrier
+  const int g = threadIdx.x / G, gl = threadIdx.x % G, d0 = gl * LD, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  float q[W][8];
+#pragma unroll
+  for (int w = 0; w < W; ++w) ld8((const T*)a.q + b * a.q_bs + hh * HD + d0 + 8 * w, q[w]);
+  const int64_t hs = a.kv_hs ? a.kv_hs : HD;
+  const uint8_t* kb = (const uint8_t*)a.k + b * a.k_bs + hh * hs + d0;
+  const uint8_t* vb = (const uint8_t*)a.v + b * a.v_bs + hh * hs + d0;
+  const uint8_t* mb = a.key_padding_mask ? a.key_padding_mask + b * a.mask_bs : (const uint8_t*)a.q;
+  const uint32_t mmask = a.key_padding_mask ? 0xffu : 0u;
+  uint2 kr[U][W], vr[U][W];
+  bool ok[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = k0 + g + u * NG;
+    const int jj = j < n ? j : k0;   // k0 < n: a key of the row
+    const uint4 kk = *reinterpret_cast<const uint4*>(kb + (int64_t)jj * a.k_ls);
+    const uint4 vv = *reinterpret_cast<const uint4*>(vb + (int64_t)jj * a.v_ls);
+    kr[u][0] = make_uint2(kk.x, kk.y), kr[u][1] = make_uint2(kk.z, kk.w);
+    vr[u][0] = make_uint2(vv.x, vv.y), vr[u][1] = make_uint2(vv.z, vv.w);
+    ok[u] = j < n && ((uint32_t)mb[a.key_padding_mask ? jj : 0] & mmask) == 0;
+  }
+  const float c = a.scale * kLog2e * sc8.k[b * sc8.bs + hh];
+  float sc[U], m = -INFINITY;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float kx[8], sv = 0.f;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      fp8x8_to_f32(kr[u][w], kx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sv = fmaf(q[w][e], kx[e], sv);
+    }
+    sv = group_sum<G>(sv, lane);
+    sc[u] = ok[u] ? sv * c : -INFINITY;
+    m = fmaxf(m, sc[u]);
+  }
+  m = groups_max<G>(m, lane);
+  if ((threadIdx.x & 63) == 0) swm[wave] = m;
+  block_sync();
+  const float M = fmaxf(fmaxf(swm[0], swm[1]), fmaxf(swm[2], swm[3]));
+  float l = 0.f, acc[LD];
+#pragma unroll
+  for (int e = 0; e < LD; ++e) acc[e] = 0.f;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float p = ok[u] ? exp2f(sc[u] - M) : 0.f;
+    l += p;
+    float vx[8];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      fp8x8_to_f32(vr[u][w], vx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[8 * w + e] = fmaf(p, vx[e], acc[8 * w + e]);
+    }
+  }
+  l = groups_sum<G>(l, lane);
+#pragma unroll
+  for (int e = 0; e < LD; ++e) acc[e] = groups_sum<G>(acc[e], lane);
+  if ((threadIdx.x & 63) < G) {
+#pragma unroll
+    for (int e = 0; e < LD; ++e) sacc[wave][d0 + e] = acc[e];
+    if (gl == 0) swl[wave] = l;
+  }
+  block_sync();
+  if (threadIdx.x < HD) {
+    const float L = (swl[0] + swl[1]) + (swl[2] + swl[3]);
+    const float o = (sacc[0][threadIdx.x] + sacc[1][threadIdx.x]) + (sacc[2][threadIdx.x] + sacc[3][threadIdx.x]);
+    float* pw = ws + ((int64_t)bh * nchunk + chunk) * (HD + 2);
+    if (threadIdx.x == 0) pw[0] = M, pw[1] = L;
+    pw[2 + threadIdx.x] = o * sc8.v[b * sc8.bs + hh];
+  }
+}
+
+template <typename T, int HD>
+void launch_decode_split_fp8(const MttsAttnFwdArgs* a, const int32_t* kv_lens, const Fp8Scales& sc8, float* ws,
+                             hipStream_t st) {
+  constexpr int CK = split_chunk(HD);
+  const int nchunk = (a->kv_len + CK - 1) / CK;
+  const int rows = a->batch * a->heads;
+  hipLaunchKernelGGL((attn_decode_split_fp8_kernel<T, HD>), dim3(rows, nchunk), dim3(256), 0, st, *a, kv_lens, sc8, ws,
+                     nchunk);
+  hipLaunchKernelGGL((attn_decode_merge_kernel<T, HD>), dim3(rows), dim3(HD < 64 ? 64 : HD), 0, st, *a, kv_lens,
+                     (const float*)ws, nchunk);
+}
+
+// ---------------------------------------------------------------------------
 // The split-key kernel for query rows that share K/V rows (n samples of one
 // request: same keys, values, mask and count, only q differs).  kv_rows[b] is
 // the K/V row of query row b, K, V, the mask and kv_lens have kv_batch rows; a
@@ -2430,6 +2554,36 @@ extern "C" int mtts_attention_decode_split(const MttsAttnDecodeSplitArgs* s, voi
     else launch_decode_split<float, hd()>(&a, s->kv_lens, ws, st);
   });
   MTTS_LAUNCH_CHECK("attention_decode_split");
+  return MTTS_OK;
+}
+
+extern "C" int mtts_attention_decode_split_fp8(const MttsAttnDecodeSplitFp8Args* s, void* stream) {
+  MTTS_CHECK(s, "attention_decode_split_fp8: null args");
+  const MttsAttnFwdArgs& a = s->s.f;
+  MTTS_CHECK(a.k && a.v, "attention_decode_split_fp8: null k / v");
+  {   // the checks of the bf16 entry point on everything but k / v, whose elements are bytes here
+    MttsAttnDecodeSplitArgs c = s->s;
+    c.f.k = c.f.v = a.q;
+    c.f.k_bs = c.f.k_ls = c.f.v_bs = c.f.v_ls = c.f.kv_hs = 0;
+    int rc = check_decode_split(&c, "attention_decode_split_fp8");
+    if (rc) return rc;
+  }
+  MTTS_CHECK(aligned16(a.k) && aligned16(a.v) && a.k_bs % 16 == 0 && a.k_ls % 16 == 0 && a.v_bs % 16 == 0 &&
+                 a.v_ls % 16 == 0 && a.kv_hs % 16 == 0 && a.kv_hs >= 0,
+             "attention_decode_split_fp8: k / v and their strides k_bs / k_ls / v_bs / v_ls / kv_hs must be "
+             "16-byte aligned");
+  MTTS_CHECK(s->k_scale && s->v_scale, "attention_decode_split_fp8: null k_scale / v_scale");
+  MTTS_CHECK(((uintptr_t)s->k_scale & 3) == 0 && ((uintptr_t)s->v_scale & 3) == 0 && s->scale_bs >= 0,
+             "attention_decode_split_fp8: k_scale / v_scale must be 4-byte aligned, scale_bs >= 0");
+  if (a.batch == 0) return MTTS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)s->s.workspace;
+  const Fp8Scales sc8{s->k_scale, s->v_scale, s->scale_bs};
+  with_head_dim(a.head_dim, [&](auto hd) {
+    if (a.dtype == MTTS_BF16) launch_decode_split_fp8<bf16_t, hd()>(&a, s->s.kv_lens, sc8, ws, st);
+    else launch_decode_split_fp8<float, hd()>(&a, s->s.kv_lens, sc8, ws, st);
+  });
+  MTTS_LAUNCH_CHECK("attention_decode_split_fp8");
   return MTTS_OK;
 }
 

@@ -23,6 +23,9 @@ Engine path (inference only: torch.no_grad, HIP tensors):
     5248 keys of train.py's conditioning) on the split-key kernel
     (attention_decode_split) from every step, packed included, each row
     reading its own key count ctx["kv_lens"] = key_counts(keep) only;
+    with generate(kv_dtype="fp8") / open_session(kv_dtype="fp8") those K / V
+    are kept as OCP FP8 bytes with a scale per (row, head) (quantize_kv_fp8)
+    and read by the kernel's fp8 form (attention_decode_split_fp8);
   * optional hipGraph capture of the whole step (static token / position /
     state buffers): replay costs one launch instead of ~25 per layer.
   * generate(): the loop around the step on the device -- one hipGraph of
@@ -50,7 +53,8 @@ from . import _lib as L
 from . import ops
 from .embed import _err_flag, embed_sum
 from .attn_kernels import (attention, attention_decode_packed, attention_decode_qproj_packed, attention_decode_split,
-                           decode_split_chunk, decode_split_workspace, key_counts)
+                           attention_decode_split_fp8, decode_split_chunk, decode_split_workspace, key_counts,
+                           quantize_kv_fp8)
 from .linear import cast_scope, cast_weight
 
 
@@ -156,6 +160,24 @@ def _check_request(m, B, n_new, prompt_tokens, start_token, logit_bias, pad_id, 
     elif int(prompt_tokens.min()) < 0 or int(prompt_tokens.max()) >= n_tok:
         raise IndexError("generate: prompt token id out of range of token_embed (index out of range in self)")
     return prompt_tokens, Tp, lens
+
+
+def check_kv_dtype(who, model, kv_dtype, n_keys):
+    """kv_dtype of generate() / open_session() against a key side of n_keys
+    keys: None, or "fp8", which the split-key attention alone reads.  Raises
+    ValueError with the reason; touches nothing."""
+    if kv_dtype is None:
+        return
+    if kv_dtype != "fp8":
+        raise ValueError(f"{who}: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+    if not DecodeEngine.OPTIONS["split_keys"]:
+        raise ValueError(f"{who}: kv_dtype='fp8' needs the split-key attention and "
+                         "DecodeEngine.OPTIONS['split_keys'] is off")
+    for l in model.layers:
+        ck = decode_split_chunk(l.cross_attn.embed_dim // l.cross_attn.num_heads)
+        if n_keys <= ck:
+            raise ValueError(f"{who}: kv_dtype='fp8' needs the split-key attention and the key side of {n_keys} keys "
+                             f"is inside the single-pass range (<= {ck} keys at this head dim)")
 
 
 def sampler_buffers(B, V, cap, dev, logprobs=False):
@@ -281,26 +303,49 @@ class DecodeEngine:
             raise IndexError("decode_step: last_token id out of range of token_embed (index out of range in self)")
 
     # -- conditioning context -------------------------------------------------
-    def _build_ctx(self, text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd):
+    def _build_ctx(self, text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd, kv_dtype=None, kv_keys=None):
+        """kv_dtype "fp8": every layer's K and V are kept as e4m3fn bytes
+        with a scale per (row, head) (quantize_kv_fp8 over the row's key
+        count) under "k8" / "v8" / "k_scale" / "v_scale", and no bf16 image
+        ("k", "v", "khm", "vhm") is.  kv_keys (a session's max_keys, fp8
+        only): nothing is projected -- text_hidden gives the batch alone --
+        and the buffers of kv_keys keys are allocated as idle rows (zero
+        bytes, scale 1, no mask); the session fills them per admission."""
         m = self.m
         B = text_hidden.shape[0]
-        th = text_hidden.to(cd)
-        th, tm = m._concat_ref(th, text_mask, ref_hidden, ref_mask, B, th.device)
-        kpm = None if tm is None else ~tm                                   # mamba_decoder.py:68-70
         d = m.token_embed.weight.shape[1]
+        dev = text_hidden.device
+        kpm = kv_lens = None
+        if kv_keys is None:
+            th = text_hidden.to(cd)
+            th, tm = m._concat_ref(th, text_mask, ref_hidden, ref_mask, B, th.device)
+            kpm = None if tm is None else ~tm                               # mamba_decoder.py:68-70
+            kv_lens = None if kpm is None else key_counts(~kpm)
         layers = []
         for l in m.layers:
             ca = l.cross_attn
+            H = ca.num_heads
             W = cast_weight(ca.in_proj_weight, cd)
             b = cast_weight(ca.in_proj_bias, cd)
-            kv = torch.addmm(b[d:], th.reshape(-1, d), W[d:].t()).view(B, -1, 2 * d)
+            if kv_keys is not None:
+                keys = dict(k8=torch.zeros(B, H, kv_keys, d // H, device=dev, dtype=torch.uint8),
+                            v8=torch.zeros(B, H, kv_keys, d // H, device=dev, dtype=torch.uint8),
+                            k_scale=torch.ones(B, H, device=dev), v_scale=torch.ones(B, H, device=dev))
+            else:
+                kv = torch.addmm(b[d:], th.reshape(-1, d), W[d:].t()).view(B, -1, 2 * d)
+                if kv_dtype == "fp8":
+                    k8, ks = quantize_kv_fp8(kv[..., :d], H, kv_lens)
+                    v8, vs = quantize_kv_fp8(kv[..., d:], H, kv_lens)
+                    keys = dict(k8=k8, v8=v8, k_scale=ks, v_scale=vs)
+                else:
+                    keys = dict(k=kv[..., :d], v=kv[..., d:])
             gb = torch.tanh(F.linear(z_style.to(l.style_mlp[0].weight.dtype), l.style_mlp[0].weight,
                                      l.style_mlp[0].bias)).to(cd)
             gamma, beta = gb[:, :d].contiguous(), gb[:, d:].contiguous()
             mm = l.mamba
             di = mm.d_inner
             layers.append(dict(
-                k=kv[..., :d], v=kv[..., d:], gamma=gamma, beta=beta,
+                keys, gamma=gamma, beta=beta,
                 Wq=W[:d], bq=b[:d], Wo=cast_weight(ca.out_proj.weight, cd), bo=cast_weight(ca.out_proj.bias, cd),
                 W1=cast_weight(l.ff[0].weight, cd), b1=cast_weight(l.ff[0].bias, cd),
                 W2=cast_weight(l.ff[2].weight, cd), b2=cast_weight(l.ff[2].bias, cd),
@@ -311,9 +356,8 @@ class DecodeEngine:
                 A=(-torch.exp(mm.A_log.detach().float())).contiguous(), D=mm.D.detach().float().contiguous(),
                 dt_bias=mm.dt_proj.bias.detach().float().contiguous(),
             ))
-        dev = text_hidden.device
         # the split-key routing is latched here, with the context: _xpk_ok and every later step agree on it
-        return dict(B=B, kpm=kpm, kv_lens=None if kpm is None else key_counts(~kpm), layers=layers, cd=cd,
+        return dict(B=B, kpm=kpm, kv_lens=kv_lens, layers=layers, cd=cd,
                     split=bool(self.OPTIONS["split_keys"]), split_ws=None,
                     tok_w=m.token_embed.weight.detach().float().contiguous(),
                     pos_w=m.pos_embed.weight.detach().float().contiguous(),
@@ -428,14 +472,20 @@ class DecodeEngine:
         with one value read one K/V row between them.  Else
         a packed step takes the single-pass kernel's packed image, a
         row-major step the single-query kernels of mtts_attention_fwd.  A
-        packed step reads the head-major copies of K / V."""
+        packed step reads the head-major copies of K / V.  A layer entry
+        with FP8 keys ("k8": kv_dtype="fp8") goes to the split-key kernel's
+        fp8 form from every step, packed or not."""
         c = self.ctx
-        k, v = (p["khm"], p["vhm"]) if packed else (p["k"], p["v"])
+        fp8 = "k8" in p                                     # _prepare / open_session saw to it that _split holds
+        k, v = (p["k8"], p["v8"]) if fp8 else (p["khm"], p["vhm"]) if packed else (p["k"], p["v"])
         S, hd = k.shape[-2], q.shape[1] // H
-        if self._split(S, hd):
+        if fp8 or self._split(S, hd):
             need = decode_split_workspace(q.shape[0], H, hd, S)
             if c["split_ws"] is None or c["split_ws"].numel() < need:
                 c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
+            if fp8:
+                return attention_decode_split_fp8(q, k, v, p["k_scale"], p["v_scale"], H, c["kpm"], c["kv_lens"],
+                                                  packed=packed, workspace=c["split_ws"])
             if c.get("kv_rows") is not None:            # a share_keys session: query row b reads K/V row kv_rows[b]
                 return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed,
                                               workspace=c["split_ws"], kv_rows=c["kv_rows"])
@@ -457,11 +507,14 @@ class DecodeEngine:
         for l, p in zip(self.m.layers, c["layers"]):
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
+            S = p["k8"].shape[2] if "k8" in p else p["k"].shape[1]
             if (any(p[k].shape[0] % 32 or p[k].shape[1] % 32 for k in names)
-                    or (p["k"].shape[1] > decode_split_chunk(hd) and not self._split(p["k"].shape[1], hd))
+                    or (S > decode_split_chunk(hd) and not self._split(S, hd))
                     or l.mamba.d_inner % 32):
                 return False
         for l, p in zip(self.m.layers, c["layers"]):   # head-major K / V: one contiguous block per (b, h)
+            if "k8" in p:                              # FP8 keys are head-major as they are
+                continue
             H = l.cross_attn.num_heads
             Bk, S, d = p["k"].shape
             p["khm"] = p["k"].reshape(Bk, S, H, d // H).permute(0, 2, 1, 3).contiguous()
@@ -478,6 +531,8 @@ class DecodeEngine:
         for l, p in zip(self.m.layers, self.ctx["layers"]):
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
+            if "k8" in p:                              # FP8 keys: a key side past the single-pass range
+                return False
             if (hd not in (64, 128) or ca.embed_dim > 2048 or ca.embed_dim % 8 or B > 32
                     or p["khm"].shape[2] > decode_split_chunk(hd) or p["Wq"].stride(0) != ca.embed_dim):
                 return False
@@ -602,17 +657,17 @@ class DecodeEngine:
         self._err_host.copy_(_err_flag(dev), non_blocking=True)
         self._err_ev.record()
 
-    def _prepare(self, conds, tok_shape, dev):
-        """Conditioning context (rebuilt when `conds`, the compute dtype or the
-        token shape changed; every graph goes with it) and the static state /
-        token / position buffers."""
+    def _prepare(self, conds, tok_shape, dev, kv_dtype=None):
+        """Conditioning context (rebuilt when `conds`, the compute dtype, the
+        token shape or kv_dtype changed; every graph goes with it) and the
+        static state / token / position buffers."""
         m = self.m
         text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
         cd = m._cd()
-        key = (cd, tok_shape)
+        key = (cd, tok_shape) if kv_dtype is None else (cd, tok_shape, kv_dtype)
         B = tok_shape[0]
         if key != self.ctx_key or not _same_ctx(self.ctx_refs, self.ctx_versions, conds):
-            self.ctx = self._build_ctx(text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd)
+            self.ctx = self._build_ctx(text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd, kv_dtype)
             self.ctx_key = key
             self.ctx_refs = conds                  # strong references (see _same_ctx)
             self.ctx_versions = tuple(None if t is None else t._version for t in conds)
@@ -777,7 +832,7 @@ class DecodeEngine:
     def generate(self, text_hidden, z_style, max_new_tokens, prompt_tokens=None, start_token=0, text_mask=None,
                  ref_hidden=None, ref_mask=None, temperature=1.0, top_k=0, top_p=1.0, logit_bias=None, eos_id=None,
                  pad_id=0, seed=0, check_every=32, prompt_lengths=None, repetition_penalty=None,
-                 repetition_window=64, return_logprobs=False):
+                 repetition_window=64, return_logprobs=False, kv_dtype=None):
         """Autoregressive generation on the device: each new token is one
         replay of a hipGraph holding the decode step and the sampler
         (csrc/sample.hip), which writes the token buffer the next step embeds,
@@ -832,6 +887,20 @@ class DecodeEngine:
         can differ where two candidates are that close.  On the fused bf16
         step both calls compute the same bits.
 
+        kv_dtype="fp8" (None: off, and nothing differs from before): the
+        conditioning K / V of every layer are kept as OCP FP8 (e4m3fn) bytes
+        with one fp32 scale per (row, head), quantised once when the context
+        is built (quantize_kv_fp8, over each row's key count), and every
+        decode step reads them through the fp8 form of the split-key
+        attention: half the K/V bytes per token.  No bf16 image of K / V is
+        kept.  The value is part of the context key: a change rebuilds the
+        context and its graphs.  The prompt prefill is the training-path
+        attention over the unquantised conditioning and stays so, in a session
+        as here, so the two agree.  ValueError when a layer's key side is
+        inside the single-pass range (latency-bound there: no fp8 kernel),
+        when OPTIONS["split_keys"] is off, or for any other value.
+        decode_step never quantises.
+
         Returns tokens (B, n) int64, n <= max(max_new_tokens), and lengths (B,);
         with return_logprobs also logprobs (B, n) fp32, 0.0 at and past a row's
         length."""
@@ -839,6 +908,8 @@ class DecodeEngine:
         V = m.head.weight.shape[0]
         B = text_hidden.shape[0]
         dev = text_hidden.device
+        check_kv_dtype("generate", m, kv_dtype,
+                       text_hidden.shape[1] + (0 if ref_hidden is None else ref_hidden.shape[1]))
         per_row = (repetition_penalty is not None
                    or not all(_is_scalar(v) for v in (temperature, top_k, top_p, seed, max_new_tokens)))
         ctl = None
@@ -859,7 +930,7 @@ class DecodeEngine:
                                                  prompt_lengths)
         self.check_errors()                         # a flag left by earlier decode_steps is theirs
         conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
-        self._prepare(conds, (B, 1), dev)
+        self._prepare(conds, (B, 1), dev, kv_dtype)
         g = self._gen_buffers(B, V, dev, bool(return_logprobs))
         stepfn = self.step_fn(bool(return_logprobs))
         eos = None if eos_id is None else int(eos_id)

@@ -23,6 +23,14 @@ reads through the session's (slots,) kv_rows buffer (the split-key attention
 loads it once per step for the whole group, bit-identically), and that slot
 stays reserved ("lent") until every member has been taken.
 
+A session opened with kv_dtype="fp8" keeps the conditioning K/V as OCP FP8
+bytes with one fp32 scale per (slot, head) -- (slots, H, max_keys, hd) uint8
+per layer and operand, a quarter of the four bf16 images a packed session
+holds -- allocated as such (no bf16 transient); an admission quantises the
+request's padded projection straight into its slot's rows over the request's
+key count, and the captured step reads them through the fp8 form of the
+split-key attention (DecodeEngine.generate's kv_dtype has the definition).
+
 plan_slots() is the refill policy as a pure host function;
 generate_requests() runs a queue of requests through a session by it.
 """
@@ -32,9 +40,9 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .attn_kernels import decode_split_chunk, key_counts
+from .attn_kernels import decode_split_chunk, key_counts, quantize_kv_fp8
 from .decode import (DecodeEngine, _check_request, _check_vocab_ids, _check_window, _is_scalar, capture_graph,
-                     sampler_buffers)
+                     check_kv_dtype, sampler_buffers)
 from .linear import cast_weight
 
 
@@ -86,7 +94,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def __init__(self, model, slots, max_keys, *, eos_id=None, pad_id=0, repetition_window=64, use_graph=True,
-                 logprobs=False, share_keys=False):
+                 logprobs=False, share_keys=False, kv_dtype=None):
         m = self.m = model
         V = m.head.weight.shape[0]
         slots, max_keys = int(slots), int(max_keys)
@@ -99,6 +107,12 @@ class DecodeSession:
             raise RuntimeError("open_session runs on the HIP kernels only (no CPU path)")
         self.slots, self.max_keys, self.V = slots, max_keys, V
         self.eos, self.pad, self.window = None if eos_id is None else int(eos_id), int(pad_id), repetition_window
+        # FP8 keys: the split-key attention's fp8 form reads them; checked before anything is allocated
+        check_kv_dtype("open_session", m, kv_dtype, max_keys)
+        if kv_dtype is not None and share_keys:
+            raise ValueError("open_session: kv_dtype='fp8' with share_keys is not built (the shared-key kernel "
+                             "measured no gain and has no fp8 form)")
+        self.kv_dtype = kv_dtype
         self.use_graph = bool(use_graph)
         self.logprobs = bool(logprobs)                      # decided here: it selects the one capture
         self.share_keys = bool(share_keys)                  # so is this: the captured step reads K/V through kv_rows
@@ -120,8 +134,14 @@ class DecodeSession:
         keep = torch.zeros(slots, max_keys, dtype=torch.bool, device=dev)
         keep[:, 0] = True                                   # a fully masked row would give NaN
         ds = m.layers[0].style_mlp[0].weight.shape[1]
-        ctx = eng._build_ctx(torch.zeros(slots, max_keys, d, device=dev, dtype=cd),
-                             torch.zeros(slots, ds, device=dev), keep, None, None, cd)
+        if kv_dtype is None:
+            ctx = eng._build_ctx(torch.zeros(slots, max_keys, d, device=dev, dtype=cd),
+                                 torch.zeros(slots, ds, device=dev), keep, None, None, cd)
+        else:                                               # the fp8 buffers allocated as idle rows, nothing projected
+            ctx = eng._build_ctx(torch.zeros(slots, 1, d, device=dev, dtype=cd),
+                                 torch.zeros(slots, ds, device=dev), None, None, None, cd, kv_dtype, kv_keys=max_keys)
+            ctx["kpm"] = ~keep
+            ctx["kv_lens"] = torch.ones(slots, dtype=torch.int32, device=dev)
         self.kpm = ctx["kpm"]                               # (slots, max_keys) bool, True = ignore: rewritten in place
         # (slots,) int32 key counts the captured step's split-key attention reads: an idle slot's only key is key 0
         self.kv_lens = ctx["kv_lens"]
@@ -131,7 +151,8 @@ class DecodeSession:
             p["Wkv"] = cast_weight(ca.in_proj_weight, cd)[d:]
             p["bkv"] = cast_weight(ca.in_proj_bias, cd)[d:]
             for name in ("k", "v", "gamma", "beta"):        # idle rows are zero, before the latch below copies them
-                p[name].zero_()
+                if name in p:
+                    p[name].zero_()
         # share_keys: query row r reads the K/V, mask and count of row kv_rows[r]; identity while idle
         self.kv_rows = torch.arange(slots, dtype=torch.int32, device=dev) if self.share_keys else None
         if self.share_keys:
@@ -328,8 +349,9 @@ class DecodeSession:
             kv = torch.addmm(p["bkv"], thp.reshape(-1, d), p["Wkv"].t())           # (max_keys, 2d): one shape, always
             lin = l.style_mlp[0]
             gb = torch.tanh(F.linear(z.to(lin.weight.dtype), lin.weight, lin.bias)).to(cd)
-            for r in kv_to:
-                self._write_kv(p, r, kv[:, :d], kv[:, d:], l.cross_attn.num_heads)
+            for r in kv_to:                                 # FP8 keys: quantised once, the other members get the bytes
+                self._write_kv(p, r, kv[:, :d], kv[:, d:], l.cross_attn.num_heads, counts,
+                               like=None if r == kv_to[0] else kv_to[0])
             for r in rows:
                 self._write_film(p, r, gb[0, :d], gb[0, d:])
         if self.share_keys:
@@ -369,9 +391,22 @@ class DecodeSession:
                 eng.pos_buf[r:r + 1].zero_()
             self.state[r] = "live"
 
-    def _write_kv(self, p, r, k, v, H):
-        """Row r of one layer's K / V (and head-major copies), in place.  k, v (max_keys, d)."""
+    def _write_kv(self, p, r, k, v, H, counts, like=None):
+        """Row r of one layer's K / V (and head-major copies), in place.  k, v
+        (max_keys, d).  FP8 keys: quantised straight into the slot's rows over
+        the request's key count `counts` ((1,) int32 on the device); the
+        bytes past it are zero.  like: a slot already written with these very
+        k, v and counts (an earlier member of an admit_samples group), whose
+        bytes and scales are copied instead."""
         K, d = k.shape
+        if "k8" in p and like is not None:
+            for name in ("k8", "v8", "k_scale", "v_scale"):
+                p[name][r].copy_(p[name][like])
+            return
+        if "k8" in p:
+            quantize_kv_fp8(k[None], H, counts, out=p["k8"][r:r + 1], scale_out=p["k_scale"][r:r + 1])
+            quantize_kv_fp8(v[None], H, counts, out=p["v8"][r:r + 1], scale_out=p["v_scale"][r:r + 1])
+            return
         p["k"][r].copy_(k)
         p["v"][r].copy_(v)
         if "khm" in p:
@@ -392,8 +427,13 @@ class DecodeSession:
         eng = self.eng
         z = torch.zeros((), device=self.dev, dtype=self.cd)
         for l, p in zip(self.m.layers, eng.ctx["layers"]):
-            K, d = p["k"].shape[1:]
-            self._write_kv(p, r, z.expand(K, d), z.expand(K, d), l.cross_attn.num_heads)
+            d = p["gamma"].shape[1]
+            if "k8" in p:                                   # zero bytes and scale 1
+                for name, fill in (("k8", 0), ("v8", 0), ("k_scale", 1.0), ("v_scale", 1.0)):
+                    p[name][r].fill_(fill)
+            else:
+                K = p["k"].shape[1]
+                self._write_kv(p, r, z.expand(K, d), z.expand(K, d), l.cross_attn.num_heads, None)
             self._write_film(p, r, z.expand(d), z.expand(d))
         self.kpm[r] = True
         self.kpm[r, 0] = False
@@ -462,7 +502,7 @@ def _keys(req):
 
 @torch.no_grad()
 def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, eos_id=None, pad_id=0,
-                      repetition_window=64, return_logprobs=False, share_keys=False):
+                      repetition_window=64, return_logprobs=False, share_keys=False, kv_dtype=None):
     """A queue of requests (dicts of DecodeSession.admit's arguments) through
     one session of `slots` rows by the policy of plan_slots.  Returns the
     token tensors in request order, the slot each request ran in and the
@@ -474,7 +514,8 @@ def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, 
     lowest idle slots; its entries in the token list, the slot list and the
     log-probability list are lists of n.  share_keys opens the session with
     it (the samples of a request then read one copy of its keys); no token
-    depends on it.  With eos_id a row may end before its cap: the
+    depends on it.  kv_dtype opens the session with it ("fp8": FP8
+    conditioning K/V).  With eos_id a row may end before its cap: the
     loop polls, so the slots then differ from plan_slots' (cap-only) answer;
     no token does."""
     requests = list(requests)
@@ -489,7 +530,7 @@ def generate_requests(model, requests, *, slots, max_keys=None, check_every=16, 
     if max_keys is None:
         max_keys = max(_keys(r) for r in requests)
     ses = model.open_session(slots, max_keys, eos_id=eos_id, pad_id=pad_id, repetition_window=repetition_window,
-                             logprobs=bool(return_logprobs), share_keys=share_keys)
+                             logprobs=bool(return_logprobs), share_keys=share_keys, kv_dtype=kv_dtype)
     lps = [None if n is None else [None] * n for n in want]
     out, where = [None if n is None else [None] * n for n in want], [None] * len(requests)
     left, who = [None] * ses.slots, [None] * ses.slots      # plan_slots' bookkeeping, with (request, member)

@@ -1,0 +1,213 @@
+"""FP8 conditioning K/V in the decode engine and in sessions
+(kv_dtype="fp8"; mtts/decode.py, mtts/session.py).  What must hold is the
+session's exactness property -- a request's tokens and log-probabilities
+depend on nothing but the request: not its slot, its neighbours, the
+session's max_keys, what an earlier request left in the slot, nor session
+versus generate() -- and closeness to the unquantised path.
+
+The decoder is that of test_gpu_long_keys.py (2 layers, d_model 512, 8 heads:
+head dim 64, 256 keys per chunk, max_keys = 2 * 256 + 8 = 520)."""
+import pytest
+import torch
+
+from test_gpu_generate import DEV
+from test_gpu_generate_rows import WINDOW
+from test_gpu_long_keys import CAP, CK, DM, DS, HEADS, KEYS, _decoder, _req
+
+pytestmark = pytest.mark.gpu
+SLOTS = 4
+HD = DM // HEADS
+
+# test_logits_stay_close_to_the_unquantised_path: the largest deviation of the fp8 session's first-step logits
+# from the plain session's, relative to the plain logits' largest magnitude, as measured on the MI355X
+MEASURED_LOGIT_DEVIATION = 6.25e-3
+
+
+@pytest.fixture(scope="module")
+def model():
+    return _decoder(torch.bfloat16)
+
+
+def _open(m, slots=SLOTS, keys=KEYS, **kw):
+    return m.open_session(slots, keys, repetition_window=WINDOW, logprobs=True, kv_dtype="fp8", **kw)
+
+
+def _solo(ses, slot, req):
+    ses.admit(slot, **req)
+    ses.run(req["max_new_tokens"])
+    assert slot in ses.poll()
+    return ses.take(slot, return_logprobs=True)
+
+
+def _generate_alone(m, req, keys=KEYS, kv_dtype="fp8"):
+    S = req["text_hidden"].shape[0]
+    text = torch.zeros(1, keys, DM, device=DEV)
+    text[0, :S] = req["text_hidden"]
+    mask = torch.zeros(1, keys, dtype=torch.bool, device=DEV)
+    mask[0, :S] = True
+    toks, lens, lps = m.generate(text, req["z_style"][None], req["max_new_tokens"], text_mask=mask,
+                                 temperature=[req["temperature"]], top_k=[req["top_k"]], seed=[req["seed"]],
+                                 repetition_penalty=[req["repetition_penalty"]], repetition_window=WINDOW,
+                                 return_logprobs=True, kv_dtype=kv_dtype)
+    assert lens.tolist() == [req["max_new_tokens"]]
+    return toks[0], lps[0]
+
+
+def _same(a, b):
+    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+def _anywhere(m, keys):
+    req = _req(keys, 0)
+    ses = _open(m)
+    want = _solo(ses, 0, req)                               # slot 0 of an otherwise idle session
+    assert want[0].shape == (CAP,) and len(torch.unique(want[0])) > 3 and torch.isfinite(want[1]).all()
+    others = [k for k in (5, CK + 1, KEYS) if k != keys]
+    ses.admit(1, **_req(others[0], 1, cap=40))
+    ses.admit(3, **_req(others[1], 2, cap=40))
+    ses.run(5)                                              # the neighbours are 5 tokens in
+    assert _same(_solo(ses, 2, req), want), "slot 2 among live neighbours"
+    assert ses.captures == (1 if m.decode_mode == "graph" else 0)
+    wide = _open(m, keys=KEYS + CK)                         # max_keys 776: one more chunk, never reached
+    assert _same(_solo(wide, 1, req), want), "a session of max_keys 776"
+    assert _same(_generate_alone(m, req), want), "generate(kv_dtype='fp8') on the request alone"
+
+
+@pytest.mark.parametrize("mode", ["graph", "eager"])
+@pytest.mark.parametrize("keys", [5, CK + 1, KEYS])
+def test_a_request_runs_the_same_anywhere_bf16(model, keys, mode):
+    model.decode_mode = mode
+    try:
+        _anywhere(model, keys)
+        assert model._engine.fused and model._engine.xpk    # the packed step
+    finally:
+        model.decode_mode = "graph"
+
+
+def test_a_request_runs_the_same_anywhere_fp32():
+    m = _decoder(None)                                      # fp32: the generic step
+    m.decode_mode = "graph"
+    _anywhere(m, CK + 1)
+    assert not m._engine.fused
+
+
+def test_stale_keys_do_not_leak(model):
+    model.decode_mode = "graph"
+    req = _req(5, 0)
+    want = _solo(_open(model), 1, req)                      # a fresh session
+    ses = _open(model)
+    _solo(ses, 1, _req(KEYS, 4, cap=9))                     # 520 keys through the slot, taken
+    assert ses.kv_lens[1].item() == 1
+    ses.admit(1, **req)
+    assert ses.kv_lens[1].item() == 5
+    for p in ses.eng.ctx["layers"]:
+        assert (p["k8"][1, :, 5:] == 0).all() and (p["v8"][1, :, 5:] == 0).all()
+    ses.run(CAP)
+    assert 1 in ses.poll()
+    assert _same(ses.take(1, return_logprobs=True), want)
+    assert ses.captures == 1
+
+
+def test_admit_samples_members_are_admits_with_their_seeds(model):
+    from mtts.ops import row_seeds
+    model.decode_mode = "graph"
+    req = _req(CK + 1, 0)
+    ses = _open(model)
+    ses.admit_samples([3, 0, 1], **req)
+    ses.run(CAP)
+    assert sorted(ses.poll()) == [0, 1, 3]
+    got = [ses.take(s, return_logprobs=True) for s in (3, 0, 1)]
+    for j, seed in enumerate(row_seeds(req["seed"], 3)):
+        assert _same(_solo(ses, 2, dict(req, seed=seed)), got[j]), f"member {j}"
+    assert not torch.equal(got[0][0], got[1][0])
+    assert ses.captures == 1
+
+
+def test_the_session_holds_fp8_keys_and_no_bf16_image(model):
+    model.decode_mode = "graph"
+    ses = _open(model)
+    assert ses.captures == 1 and ses.eng.fused and ses.eng.xpk and not ses.eng.fuse_q
+    for p in ses.eng.ctx["layers"]:
+        for name in ("k8", "v8"):
+            assert p[name].shape == (SLOTS, HEADS, KEYS, HD) and p[name].dtype == torch.uint8
+            assert p[name].is_contiguous() and (p[name] == 0).all()
+        for name in ("k_scale", "v_scale"):
+            assert p[name].shape == (SLOTS, HEADS) and p[name].dtype == torch.float32 and (p[name] == 1).all()
+        assert not any(name in p for name in ("k", "v", "khm", "vhm"))
+    ses.admit(2, **_req(300, 1))
+    p = ses.eng.ctx["layers"][0]
+    assert (p["k8"][2, :, :300] != 0).any() and (p["k8"][2, :, 300:] == 0).all() and (p["k_scale"][2] != 1).all()
+    assert (p["k8"][[0, 1, 3]] == 0).all() and (p["k_scale"][[0, 1, 3]] == 1).all()
+    ses.run(CAP)
+    ses.take(2)
+    assert (p["k8"][2] == 0).all() and (p["v8"][2] == 0).all()         # idle again: zero bytes, scale 1
+    assert (p["k_scale"][2] == 1).all() and (p["v_scale"][2] == 1).all()
+
+
+def test_generate_keeps_fp8_keys_and_rebuilds_on_a_change(model):
+    model.decode_mode = "graph"
+    text, z = torch.randn(2, KEYS, DM, device=DEV), torch.randn(2, DS, device=DEV)
+    a, _ = model.generate(text, z, 4, kv_dtype="fp8")
+    eng = model._engine
+    ctx = eng.ctx
+    assert all("k8" in p and not any(n in p for n in ("k", "v", "khm", "vhm")) for p in ctx["layers"])
+    assert ctx["layers"][0]["k8"].shape == (2, HEADS, KEYS, HD) and eng.ctx_key[-1] == "fp8"
+    assert eng.fused and eng.xpk and not eng.fuse_q
+    again, _ = model.generate(text, z, 4, kv_dtype="fp8")
+    assert eng.ctx is ctx and torch.equal(again, a)         # the same tensors and value: the context is kept
+    b, _ = model.generate(text, z, 4)                       # the same tensors, kv_dtype off: a new context
+    assert eng.ctx is not ctx and "k" in eng.ctx["layers"][0] and "k8" not in eng.ctx["layers"][0]
+    assert len(eng.ctx_key) == 2 and a.shape == b.shape
+
+
+def _untouched(fn, match):
+    from mtts.session import DecodeSession
+    torch.cuda.synchronize()
+    before, caps = torch.cuda.memory_allocated(), DecodeSession.CAPTURES
+    with pytest.raises(ValueError, match=match):
+        fn()
+    assert torch.cuda.memory_allocated() == before and DecodeSession.CAPTURES == caps
+
+
+def test_refusals_come_before_anything_is_allocated(model, monkeypatch):
+    from mtts.decode import DecodeEngine
+    model.decode_mode = "graph"
+    text, z = torch.randn(1, KEYS, DM, device=DEV), torch.randn(1, DS, device=DEV)
+    short = torch.randn(1, CK, DM, device=DEV)
+    model.generate(text, z, 2)                              # an engine and a context to leave alone
+    ctx = model._engine.ctx
+    _untouched(lambda: model.open_session(SLOTS, CK, kv_dtype="fp8"), "inside the single-pass range")
+    _untouched(lambda: model.generate(short, z, 2, kv_dtype="fp8"), "inside the single-pass range")
+    _untouched(lambda: model.open_session(SLOTS, KEYS, kv_dtype="fp16"), "kv_dtype must be None or 'fp8'")
+    _untouched(lambda: model.generate(text, z, 2, kv_dtype="int8"), "kv_dtype must be None or 'fp8'")
+    _untouched(lambda: model.open_session(SLOTS, KEYS, kv_dtype="fp8", share_keys=True), "not built")
+    _untouched(lambda: model.generate_requests([_req(300, 0)], slots=2, max_keys=KEYS, kv_dtype="fp8",
+                                               share_keys=True), "not built")
+    monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", False)
+    _untouched(lambda: model.open_session(SLOTS, KEYS, kv_dtype="fp8"), "split_keys'\\] is off")
+    _untouched(lambda: model.generate(text, z, 2, kv_dtype="fp8"), "split_keys'\\] is off")
+    assert model._engine.ctx is ctx
+
+
+def test_logits_stay_close_to_the_unquantised_path(model):
+    """After one replay from a one-token start, the logits of 8 requests in
+    an fp8 session against a plain session's (the behaviour without
+    kv_dtype).  The bound cannot be derived; the kernels are deterministic, so
+    it is twice the deviation measured on the MI355X (profiles/kv_fp8_ab.txt),
+    relative to the plain logits' largest magnitude: a guard for later
+    refactors, not against noise.  Measured: 6.25e-3 (one bf16 step of a
+    logit near the largest), so the bound is 1.25e-2."""
+    model.decode_mode = "graph"
+    keys = [5, CK + 1, KEYS, 300, 100, KEYS - 1, CK, 400]
+    logits = {}
+    for kind in (None, "fp8"):
+        ses = model.open_session(8, KEYS, repetition_window=WINDOW, kv_dtype=kind)
+        for s, k in enumerate(keys):
+            ses.admit(s, **_req(k, s))
+        ses.run(1)
+        logits[kind] = ses.logits.float().clone()
+    assert torch.isfinite(logits["fp8"]).all()
+    dev = ((logits["fp8"] - logits[None]).abs().max() / logits[None].abs().max()).item()
+    print(f"fp8 vs plain session, first-step logits: {dev:.6e} of the largest plain logit")
+    assert MEASURED_LOGIT_DEVIATION is not None, "no measured deviation recorded"
+    assert 0 < dev <= 2 * MEASURED_LOGIT_DEVIATION

@@ -42,8 +42,15 @@ samples of one request, admit_samples): us per token of a share_keys session
 plain session whose members hold copies (what n unrelated requests cost), five
 interleaved repeats in one process, median, min and max; then the wall time of
 one admit_samples of 4 against four admits.
-python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys | --logprobs | --shared-keys]
-                            [--out FILE]"""
+--kv-fp8 runs the FP8 K/V leg instead (--steps 256): the shapes of --long-keys
+(train.py's widths at max_keys 5248 with 1, 8 and 32 slots, C4's at max_keys
+1024 with 32 slots; every request at max_keys, and key counts uniform in
+[600, max_keys]), us per token of a session with bf16 K/V against one opened
+with kv_dtype="fp8", both on the split-key kernel, five interleaved repeats in
+one process, median, min and max; the K/V bytes each session holds; then the
+wall time of one admit and of one admit_samples of 4, both ways.
+python tools/generate_ab.py [--steps 512] [--ragged | --rows | --session | --long-keys | --logprobs | --shared-keys |
+                             --kv-fp8] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -316,6 +323,104 @@ def long_keys_leg(n, dev, lines):
             torch.cuda.empty_cache()
 
 
+def kv_fp8_leg(n, dev, lines):
+    """bf16 K/V against kv_dtype="fp8" at the shapes of long_keys_leg, both on
+    the split-key kernel: us per token, the K/V bytes held, the admission."""
+    import statistics
+    import time
+
+    import mamba_decoder
+    vocab, reps = 1024, 5
+    lines.append(f"FP8 conditioning K/V, bf16 step, vocab {vocab}, {n} steps, top_k=50 top_p=0.9, every slot live, us per "
+                 f"token ({reps} interleaved repeats in one process: median [min max]; spread = max - min).  (b) bf16 "
+                 "K/V, (f) kv_dtype='fp8', both on the split-key kernel; 'max': every request at max_keys, 'r': key "
+                 "counts uniform in [600, max_keys] (seed 5).  K/V held: bytes of every layer's K/V tensors in the "
+                 "session (bf16: k, v and the head-major copies; fp8: bytes and scales)")
+    shapes = (("train.py widths (8L d=512 8 heads)", dict(n_layers=8, d_model=512, n_heads=8), 5248, (1, 8, 32)),
+              ("C4 widths (12L d=1024 8 heads)", dict(n_layers=12, d_model=1024, n_heads=8), 1024, (32,)))
+    names = ("k", "v", "khm", "vhm", "k8", "v8", "k_scale", "v_scale")
+
+    def fmt(v):
+        return f"{statistics.median(v):8.1f} [{min(v):.1f} {max(v):.1f}]  spread {max(v) - min(v):.1f}"
+
+    for name, width, max_keys, slot_counts in shapes:
+        torch.manual_seed(0)
+        m = mamba_decoder.MambaTTSDecoder(vocab, d_ff=2048, d_style=256, **width).to(dev).eval()
+        m.compute_dtype = torch.bfloat16
+        d = width["d_model"]
+        for slots in slot_counts:
+            g = torch.Generator().manual_seed(5)
+            text = torch.randn(slots, max_keys, d, generator=g).to(dev)
+            z = torch.randn(slots, 256, generator=g).to(dev)
+            counts = torch.randint(600, max_keys + 1, (slots,), generator=g).tolist()
+            ses = {"b": m.open_session(slots, max_keys, repetition_window=64),
+                   "f": m.open_session(slots, max_keys, repetition_window=64, kv_dtype="fp8")}
+            assert ses["b"].eng.xpk and ses["f"].eng.xpk
+            held = {leg: sum(p[k].numel() * p[k].element_size() for p in s.eng.ctx["layers"] for k in names if k in p)
+                    for leg, s in ses.items()}
+            kw = dict(temperature=1.0, top_k=50, top_p=0.9)
+
+            def run(leg, ragged):
+                s = ses[leg]
+                for r in range(slots):
+                    keys = counts[r] if ragged else max_keys
+                    s.admit(r, text[r, :keys], z[r], max_new_tokens=n, seed=r + 1, **kw)
+                t = timed(lambda: s.run(n))
+                for r in s.poll():
+                    s.take(r)
+                return t * 1e3 / n
+
+            cases = [(leg, ragged) for ragged in (False, True) for leg in ("b", "f")]
+            for c in cases:
+                run(*c)                                        # warm up
+            res = {c: [] for c in cases}
+            for _ in range(reps):
+                for c in cases:
+                    res[c].append(run(*c))
+            mean = sum(counts) / slots
+            for ragged, what in ((False, "max"), (True, f"r (mean {mean:.0f} keys)")):
+                b, f = res[("b", ragged)], res[("f", ragged)]
+                lines.append(f"{name}, max_keys {max_keys}, {slots:2d} slots, {what:20s} (b) {fmt(b)}   (f) {fmt(f)}   "
+                             f"(f) - (b) {statistics.median(f) - statistics.median(b):+.1f}")
+                print(lines[-1], flush=True)
+            lines.append(f"{name}, max_keys {max_keys}, {slots:2d} slots, K/V held: (b) {held['b'] / 2**20:.1f} MiB   "
+                         f"(f) {held['f'] / 2**20:.1f} MiB")
+            print(lines[-1], flush=True)
+            if slots >= 4 and slots == max(slot_counts):
+
+                def admission(leg, together):
+                    s = ses[leg]
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    if together:
+                        s.admit_samples([0, 1, 2, 3], text[0], z[0], max_new_tokens=2, seed=1, **kw)
+                    else:
+                        s.admit(0, text[0], z[0], max_new_tokens=2, seed=1, **kw)
+                    torch.cuda.synchronize()
+                    t = (time.perf_counter() - t0) * 1e3
+                    s.run(2)
+                    for r in s.poll():
+                        s.take(r)
+                    return t
+
+                acases = [(leg, tog) for tog in (False, True) for leg in ("b", "f")]
+                for c in acases:
+                    admission(*c)
+                ares = {c: [] for c in acases}
+                for _ in range(reps):
+                    for c in acases:
+                        ares[c].append(admission(*c))
+                for tog, what in ((False, "one admit"), (True, "admit_samples of 4")):
+                    lines.append(f"{name}, max_keys {max_keys}, {slots:2d} slots, {what}, wall ms with a synchronize on "
+                                 "both sides: " + "   ".join(
+                                     f"({leg}) {statistics.median(ares[(leg, tog)]):.2f} [{min(ares[(leg, tog)]):.2f} "
+                                     f"{max(ares[(leg, tog)]):.2f}]" for leg in ("b", "f")))
+                    print(lines[-1], flush=True)
+            lines.append("graphs captured: " + " ".join(str(s.captures) for s in ses.values()))
+            del ses
+            torch.cuda.empty_cache()
+
+
 def shared_keys_leg(n, dev, lines):
     """n samples of one request: a share_keys session against a plain one
     whose members hold copies of the K/V, then the admission itself."""
@@ -472,14 +577,16 @@ def main():
                     "(profiles/sample_logprobs_ab.txt)")
     ap.add_argument("--shared-keys", action="store_true", help="run the parallel-samples leg instead "
                     "(profiles/shared_keys_ab.txt: --steps 256)")
+    ap.add_argument("--kv-fp8", action="store_true", help="run the FP8 K/V leg instead "
+                    "(profiles/kv_fp8_ab.txt: --steps 256)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import mamba_decoder
     dev = "cuda"
     n = args.steps
-    if args.ragged or args.rows or args.session or args.long_keys or args.logprobs or args.shared_keys:
+    if args.ragged or args.rows or args.session or args.long_keys or args.logprobs or args.shared_keys or args.kv_fp8:
         lines = []
-        (ragged_leg if args.ragged else rows_leg if args.rows else session_leg if args.session
+        (kv_fp8_leg if args.kv_fp8 else ragged_leg if args.ragged else rows_leg if args.rows else session_leg if args.session
          else long_keys_leg if args.long_keys else shared_keys_leg if args.shared_keys else logprobs_leg)(n, dev, lines)
         if args.out:
             with open(args.out, "w") as f:
