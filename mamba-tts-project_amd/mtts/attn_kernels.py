@@ -186,17 +186,10 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
     call without kv_rows gives on k[kv_rows], v[kv_rows], ...  A value
     outside [0, R) gives the row no keys (NaN, lse -inf).  None: today's
     symbol, k / v per query row."""
-    for t in (q, k, v):
-        if not t.is_cuda:
-            raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
-    if q.dim() != 2:
-        raise ValueError("attention_decode_split: q must be (B, d)")
-    B, d = q.shape
-    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
-        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
+    who = "attention_decode_split"
+    B = _split_rows(who, q, n_heads, k, v)
     if not (q.dtype == k.dtype == v.dtype):
         raise TypeError("q, k, v must share a dtype")
-    hd = d // n_heads
     R = B
     if kv_rows is not None:
         if kv_rows.dtype != torch.int32 or tuple(kv_rows.shape) != (B,) or not kv_rows.is_cuda \
@@ -205,35 +198,49 @@ def attention_decode_split(q, k, v, n_heads, kpm=None, kv_lens=None, packed=Fals
         R = k.shape[0]
         if R < 1:
             raise ValueError("attention_decode_split: kv_rows needs at least one K/V row")
-    a, out, yp, keep = _decode_args("attention_decode_split", q, k, v, n_heads, kpm, want_out=not packed,
-                                    want_packed=packed, kv_batch=R)
-    S = a.kv_len
-    if S < 1:
-        raise ValueError("attention_decode_split: the key side is empty")
-    lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
-    a.lse = L.ptr(lse)
-    if kv_lens is not None:
-        if kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (R,) or not kv_lens.is_cuda \
-                or not kv_lens.is_contiguous():
-            raise ValueError(f"attention_decode_split: kv_lens must be ({R},) int32 on the device")
-    sa = L.AttnDecodeSplitArgs()
-    sa.f = a
-    sa.kv_lens = L.ptr(kv_lens)
-    nbytes = decode_split_workspace(B, n_heads, hd, S)
-    ws = workspace
-    if ws is None:
-        ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
-    elif ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
-        raise ValueError(f"attention_decode_split: workspace must be >= {nbytes} contiguous uint8 bytes on the device")
-    sa.workspace, sa.workspace_bytes = ws.data_ptr(), ws.numel()
+    sa, res, keep = _split_args(who, q, k, v, n_heads, kpm, kv_lens, packed, want_lse, workspace, R)
     if kv_rows is None:
         L.call("mtts_attention_decode_split", sa)
     else:
         sh = L.AttnDecodeSplitSharedArgs()
         sh.s, sh.kv_rows, sh.kv_batch = sa, kv_rows.data_ptr(), R
         L.call("mtts_attention_decode_split_shared", sh)
+    return res
+
+
+def _split_rows(who, q, n_heads, *operands):
+    """What a split-key call checks first, under the caller's name `who`; returns q's rows."""
+    for t in (q,) + operands:
+        if not t.is_cuda:
+            raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
+    if q.dim() != 2:
+        raise ValueError(f"{who}: q must be (B, d)")
+    B, d = q.shape
+    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
+        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
+    return B
+
+
+def _split_args(who, q, k, v, n_heads, kpm, kv_lens, packed, want_lse, workspace, R):
+    """What a split-key call checks after its own checks, in this order: the single-query front end over R rows
+    of k / v, the key side, kv_lens, the workspace.  Returns AttnDecodeSplitArgs, what the caller returns after
+    its launch, and the tensors that must live until then."""
+    B = q.shape[0]
+    a, out, yp, keep = _decode_args(who, q, k, v, n_heads, kpm, want_out=not packed, want_packed=packed, kv_batch=R)
+    if a.kv_len < 1:
+        raise ValueError(f"{who}: the key side is empty")
+    lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
+    a.lse = L.ptr(lse)
+    _check_kv_lens(who, kv_lens, R)
+    sa = L.AttnDecodeSplitArgs()
+    sa.f, sa.kv_lens = a, L.ptr(kv_lens)
+    nbytes = decode_split_workspace(B, n_heads, q.shape[1] // n_heads, a.kv_len)
+    ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise ValueError(f"{who}: workspace must be >= {nbytes} contiguous uint8 bytes on the device")
+    sa.workspace, sa.workspace_bytes = ws.data_ptr(), ws.numel()
     res = yp if packed else out[:, 0]
-    return (res, lse) if want_lse else res
+    return sa, ((res, lse) if want_lse else res), (keep, ws)
 
 
 def _check_kv_lens(who, kv_lens, R):
@@ -297,43 +304,18 @@ def attention_decode_split_fp8(q, k8, v8, k_scale, v_scale, n_heads, kpm=None, k
     the result is softmax(q K^T / sqrt(hd)) V^ with fp32 accumulation; kpm,
     kv_lens, packed, want_lse and workspace (decode_split_workspace bytes) as
     attention_decode_split.  No byte at or past a row's count is read."""
-    for t in (q, k8, v8, k_scale, v_scale):
-        if not t.is_cuda:
-            raise RuntimeError("libmtts ops need CUDA (HIP) tensors; there is no CPU path")
-    if q.dim() != 2:
-        raise ValueError("attention_decode_split_fp8: q must be (B, d)")
-    B, d = q.shape
-    if d % n_heads or (d // n_heads) not in _HEAD_DIMS:
-        raise ValueError(f"head_dim {d}/{n_heads} not supported (need one of {_HEAD_DIMS})")
-    hd = d // n_heads
+    who = "attention_decode_split_fp8"
+    B = _split_rows(who, q, n_heads, k8, v8, k_scale, v_scale)
     if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or k8.dim() != 4:
         raise TypeError("attention_decode_split_fp8: k8 / v8 must be (B, H, S, hd) torch.uint8 (e4m3fn bytes)")
     for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
         if s.dtype != torch.float32 or tuple(s.shape) != (B, n_heads) or not s.is_contiguous():
             raise ValueError(f"attention_decode_split_fp8: {name} must be ({B}, {n_heads}) fp32, contiguous")
-    a, out, yp, keep = _decode_args("attention_decode_split_fp8", q, k8, v8, n_heads, kpm, want_out=not packed,
-                                    want_packed=packed)
-    S = a.kv_len
-    if S < 1:
-        raise ValueError("attention_decode_split_fp8: the key side is empty")
-    lse = torch.empty(B, n_heads, device=q.device, dtype=torch.float32) if want_lse else None
-    a.lse = L.ptr(lse)
-    _check_kv_lens("attention_decode_split_fp8", kv_lens, B)
     fa = L.AttnDecodeSplitFp8Args()
-    fa.s.f = a
-    fa.s.kv_lens = L.ptr(kv_lens)
-    nbytes = decode_split_workspace(B, n_heads, hd, S)
-    ws = workspace
-    if ws is None:
-        ws = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
-    elif ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous() or ws.numel() < nbytes:
-        raise ValueError(f"attention_decode_split_fp8: workspace must be >= {nbytes} contiguous uint8 bytes on the "
-                         "device")
-    fa.s.workspace, fa.s.workspace_bytes = ws.data_ptr(), ws.numel()
+    fa.s, res, keep = _split_args(who, q, k8, v8, n_heads, kpm, kv_lens, packed, want_lse, workspace, B)
     fa.k_scale, fa.v_scale, fa.scale_bs = k_scale.data_ptr(), v_scale.data_ptr(), n_heads
     L.call("mtts_attention_decode_split_fp8", fa)
-    res = yp if packed else out[:, 0]
-    return (res, lse) if want_lse else res
+    return res
 
 
 def attention_fwd(q, k, v, n_heads, kpm=None, want_lse=False):

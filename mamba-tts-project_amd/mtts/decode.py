@@ -5,7 +5,8 @@ quant_embed, pos = step_index), runs every layer with its Mamba state and
 cross-attends to [ref ‖ text].  The reference recomputes, every step, the
 K/V projections of the (constant) conditioning sequence and the FiLM
 gamma/beta of the (constant) style vector; the engine computes them once per
-conditioning context and keeps them in HBM with the per-layer SSM/conv state.
+context and keeps them in HBM (ctx["cond"], the Conditioning of mtts/conditioning.py,
+beside the model's cast constants ctx["layers"]) with the per-layer SSM/conv state.
 
 Engine path (inference only: torch.no_grad, HIP tensors):
   * context cache keyed on the object identity (strong references are
@@ -22,7 +23,7 @@ Engine path (inference only: torch.no_grad, HIP tensors):
   * a key side past the single-pass range (decode_split_chunk(hd) keys; the
     5248 keys of train.py's conditioning) on the split-key kernel
     (attention_decode_split) from every step, packed included, each row
-    reading its own key count ctx["kv_lens"] = key_counts(keep) only;
+    reading its own key count kv_lens = key_counts(keep) only;
     with generate(kv_dtype="fp8") / open_session(kv_dtype="fp8") those K / V
     are kept as OCP FP8 bytes with a scale per (row, head) (quantize_kv_fp8)
     and read by the kernel's fp8 form (attention_decode_split_fp8);
@@ -52,9 +53,8 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import ops
 from .embed import _err_flag, embed_sum
-from .attn_kernels import (attention, attention_decode_packed, attention_decode_qproj_packed, attention_decode_split,
-                           attention_decode_split_fp8, decode_split_chunk, decode_split_workspace, key_counts,
-                           quantize_kv_fp8)
+from .attn_kernels import attention_decode_qproj_packed, decode_split_chunk
+from .conditioning import Conditioning
 from .linear import cast_scope, cast_weight
 
 
@@ -170,14 +170,18 @@ def check_kv_dtype(who, model, kv_dtype, n_keys):
         return
     if kv_dtype != "fp8":
         raise ValueError(f"{who}: kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+    check_split_keys(who, "kv_dtype='fp8'", model, n_keys, f"the key side of {n_keys} keys")
+
+
+def check_split_keys(who, what, model, n_keys, side):
+    """`what`, which the split-key attention alone serves, against `side`, the caller's words for its n_keys keys."""
     if not DecodeEngine.OPTIONS["split_keys"]:
-        raise ValueError(f"{who}: kv_dtype='fp8' needs the split-key attention and "
-                         "DecodeEngine.OPTIONS['split_keys'] is off")
+        raise ValueError(f"{who}: {what} needs the split-key attention and DecodeEngine.OPTIONS['split_keys'] is off")
     for l in model.layers:
         ck = decode_split_chunk(l.cross_attn.embed_dim // l.cross_attn.num_heads)
         if n_keys <= ck:
-            raise ValueError(f"{who}: kv_dtype='fp8' needs the split-key attention and the key side of {n_keys} keys "
-                             f"is inside the single-pass range (<= {ck} keys at this head dim)")
+            raise ValueError(f"{who}: {what} needs the split-key attention and {side} is inside the single-pass range "
+                             f"(<= {ck} keys at this head dim)")
 
 
 def sampler_buffers(B, V, cap, dev, logprobs=False):
@@ -303,49 +307,21 @@ class DecodeEngine:
             raise IndexError("decode_step: last_token id out of range of token_embed (index out of range in self)")
 
     # -- conditioning context -------------------------------------------------
-    def _build_ctx(self, text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd, kv_dtype=None, kv_keys=None):
-        """kv_dtype "fp8": every layer's K and V are kept as e4m3fn bytes
-        with a scale per (row, head) (quantize_kv_fp8 over the row's key
-        count) under "k8" / "v8" / "k_scale" / "v_scale", and no bf16 image
-        ("k", "v", "khm", "vhm") is.  kv_keys (a session's max_keys, fp8
-        only): nothing is projected -- text_hidden gives the batch alone --
-        and the buffers of kv_keys keys are allocated as idle rows (zero
-        bytes, scale 1, no mask); the session fills them per admission."""
+    def _build_ctx(self, cond):
+        """The context over `cond` (Conditioning.from_batch or .idle), whose layers are added here."""
         m = self.m
-        B = text_hidden.shape[0]
+        cd = cond.cd
         d = m.token_embed.weight.shape[1]
-        dev = text_hidden.device
-        kpm = kv_lens = None
-        if kv_keys is None:
-            th = text_hidden.to(cd)
-            th, tm = m._concat_ref(th, text_mask, ref_hidden, ref_mask, B, th.device)
-            kpm = None if tm is None else ~tm                               # mamba_decoder.py:68-70
-            kv_lens = None if kpm is None else key_counts(~kpm)
+        dev = m.token_embed.weight.device
         layers = []
         for l in m.layers:
             ca = l.cross_attn
-            H = ca.num_heads
             W = cast_weight(ca.in_proj_weight, cd)
             b = cast_weight(ca.in_proj_bias, cd)
-            if kv_keys is not None:
-                keys = dict(k8=torch.zeros(B, H, kv_keys, d // H, device=dev, dtype=torch.uint8),
-                            v8=torch.zeros(B, H, kv_keys, d // H, device=dev, dtype=torch.uint8),
-                            k_scale=torch.ones(B, H, device=dev), v_scale=torch.ones(B, H, device=dev))
-            else:
-                kv = torch.addmm(b[d:], th.reshape(-1, d), W[d:].t()).view(B, -1, 2 * d)
-                if kv_dtype == "fp8":
-                    k8, ks = quantize_kv_fp8(kv[..., :d], H, kv_lens)
-                    v8, vs = quantize_kv_fp8(kv[..., d:], H, kv_lens)
-                    keys = dict(k8=k8, v8=v8, k_scale=ks, v_scale=vs)
-                else:
-                    keys = dict(k=kv[..., :d], v=kv[..., d:])
-            gb = torch.tanh(F.linear(z_style.to(l.style_mlp[0].weight.dtype), l.style_mlp[0].weight,
-                                     l.style_mlp[0].bias)).to(cd)
-            gamma, beta = gb[:, :d].contiguous(), gb[:, d:].contiguous()
+            cond.add_layer(l, W[d:], b[d:])
             mm = l.mamba
             di = mm.d_inner
             layers.append(dict(
-                keys, gamma=gamma, beta=beta,
                 Wq=W[:d], bq=b[:d], Wo=cast_weight(ca.out_proj.weight, cd), bo=cast_weight(ca.out_proj.bias, cd),
                 W1=cast_weight(l.ff[0].weight, cd), b1=cast_weight(l.ff[0].bias, cd),
                 W2=cast_weight(l.ff[2].weight, cd), b2=cast_weight(l.ff[2].bias, cd),
@@ -356,9 +332,8 @@ class DecodeEngine:
                 A=(-torch.exp(mm.A_log.detach().float())).contiguous(), D=mm.D.detach().float().contiguous(),
                 dt_bias=mm.dt_proj.bias.detach().float().contiguous(),
             ))
-        # the split-key routing is latched here, with the context: _xpk_ok and every later step agree on it
-        return dict(B=B, kpm=kpm, kv_lens=kv_lens, layers=layers, cd=cd,
-                    split=bool(self.OPTIONS["split_keys"]), split_ws=None,
+        cond.source = None
+        return dict(B=cond.rows, cond=cond, layers=layers, cd=cd,
                     tok_w=m.token_embed.weight.detach().float().contiguous(),
                     pos_w=m.pos_embed.weight.detach().float().contiguous(),
                     q0_w=torch.zeros(1, d, device=dev), q0_id=torch.zeros(1, device=dev, dtype=torch.int32),
@@ -421,7 +396,7 @@ class DecodeEngine:
         x is the bf16 residual stream, exactly as the LayerNorm kernels'
         x_sum of the generic step."""
         m, c = self.m, self.ctx
-        cd = c["cd"]
+        cond = c["cond"]
         x = self._embed(tok)
 
         def ln(norm, gamma=None, beta=None):
@@ -434,7 +409,7 @@ class DecodeEngine:
             return self._step_xpk(x, states, ln)
 
         fuse_conv = self.OPTIONS["fuse_conv"]
-        for i, (l, p) in enumerate(zip(m.layers, c["layers"])):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
             conv_state, ssm_state = states[i]
             mm = l.mamba
             di, N, r = mm.d_inner, mm.d_state, mm.dt_rank
@@ -449,55 +424,16 @@ class DecodeEngine:
                                  xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"])
             x = ops.gemm_rows(y, w(p, "Wout"), res=x)
             q = ops.gemm_rows(x, w(p, "Wq"), p["bq"], ln=ln(l.norm_cross))
-            o = self._attend(q, p, l.cross_attn.num_heads, packed=False)
+            o = cond.attend(cl, q, packed=False)
             x = ops.gemm_rows(o, w(p, "Wo"), p["bo"], res=x)
-            f = ops.gemm_rows(x, w(p, "W1"), p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma"], p["beta"]))
+            f = ops.gemm_rows(x, w(p, "W1"), p["b1"], "gelu", ln=ln(l.norm_ff, cl.gamma, cl.beta))
             x = ops.gemm_rows(f, w(p, "W2"), p["b2"], res=x)
         return ops.gemm_rows(x, w(c, "Wh"), c["bh"], ln=ln(m.norm_out))[:, None]
-
-    def _split(self, S, hd):
-        """A key side of S keys goes to the split-key kernel: past the
-        single-pass range, with OPTIONS["split_keys"] on when the context
-        was built.  A head dim no attention kernel takes is not this
-        predicate's to refuse: False, and the attention call raises."""
-        return self.ctx["split"] and hd in (16, 32, 64, 128) and S > decode_split_chunk(hd)
-
-    def _attend(self, q, p, H, packed):
-        """Every step's cross-attention of q (B, d) over the keys of the
-        layer's entry p, and the one place that picks its kernel.  A long key
-        side (_split): the split-key kernel with the context's key counts and
-        its workspace, one allocation per context (every layer's partials
-        have the same shape and the layers run in turn on one stream); a
-        context with "kv_rows" (a share_keys session) passes it on, so rows
-        with one value read one K/V row between them.  Else
-        a packed step takes the single-pass kernel's packed image, a
-        row-major step the single-query kernels of mtts_attention_fwd.  A
-        packed step reads the head-major copies of K / V.  A layer entry
-        with FP8 keys ("k8": kv_dtype="fp8") goes to the split-key kernel's
-        fp8 form from every step, packed or not."""
-        c = self.ctx
-        fp8 = "k8" in p                                     # _prepare / open_session saw to it that _split holds
-        k, v = (p["k8"], p["v8"]) if fp8 else (p["khm"], p["vhm"]) if packed else (p["k"], p["v"])
-        S, hd = k.shape[-2], q.shape[1] // H
-        if fp8 or self._split(S, hd):
-            need = decode_split_workspace(q.shape[0], H, hd, S)
-            if c["split_ws"] is None or c["split_ws"].numel() < need:
-                c["split_ws"] = torch.empty(need, device=q.device, dtype=torch.uint8)
-            if fp8:
-                return attention_decode_split_fp8(q, k, v, p["k_scale"], p["v_scale"], H, c["kpm"], c["kv_lens"],
-                                                  packed=packed, workspace=c["split_ws"])
-            if c.get("kv_rows") is not None:            # a share_keys session: query row b reads K/V row kv_rows[b]
-                return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed,
-                                              workspace=c["split_ws"], kv_rows=c["kv_rows"])
-            return attention_decode_split(q, k, v, H, c["kpm"], c["kv_lens"], packed=packed, workspace=c["split_ws"])
-        if packed:
-            return attention_decode_packed(q, k, v, H, c["kpm"])
-        return attention(q[:, None], k, v, H, c["kpm"])[:, 0]
 
     def _xpk_ok(self):
         """Every projection packed and every operand shape the packed
         activation images take (K, N % 32; a key side the single-pass or the
-        split-key kernel takes): the step of _step_xpk applies."""
+        split-key kernel takes): the step of _step_xpk applies; makes nothing."""
         if not self.OPTIONS["xpacked"]:
             return False
         c = self.ctx
@@ -507,34 +443,21 @@ class DecodeEngine:
         for l, p in zip(self.m.layers, c["layers"]):
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
-            S = p["k8"].shape[2] if "k8" in p else p["k"].shape[1]
             if (any(p[k].shape[0] % 32 or p[k].shape[1] % 32 for k in names)
-                    or (S > decode_split_chunk(hd) and not self._split(S, hd))
+                    or (c["cond"].keys > decode_split_chunk(hd) and not c["cond"].splits(hd))
                     or l.mamba.d_inner % 32):
                 return False
-        for l, p in zip(self.m.layers, c["layers"]):   # head-major K / V: one contiguous block per (b, h)
-            if "k8" in p:                              # FP8 keys are head-major as they are
-                continue
-            H = l.cross_attn.num_heads
-            Bk, S, d = p["k"].shape
-            p["khm"] = p["k"].reshape(Bk, S, H, d // H).permute(0, 2, 1, 3).contiguous()
-            p["vhm"] = p["v"].reshape(Bk, S, H, d // H).permute(0, 2, 1, 3).contiguous()
-        for p in c["layers"]:   # FiLM rows as packed images (per-context constants)
-            if "gamma_p" not in p:
-                p["gamma_p"] = ops.PackedAct.pack(p["gamma"])
-                p["beta_p"] = ops.PackedAct.pack(p["beta"])
         return True
 
     def _fuse_q_ok(self, B):
         """Shapes mtts_attention_decode_qproj takes (head_dim 64 / 128,
-        d_model <= 2048, <= 32 sequences, the single-pass key range)."""
+        d_model <= 2048, <= 32 sequences, no FP8 keys, the single-pass range)."""
+        cond = self.ctx["cond"]
         for l, p in zip(self.m.layers, self.ctx["layers"]):
             ca = l.cross_attn
             hd = ca.embed_dim // ca.num_heads
-            if "k8" in p:                              # FP8 keys: a key side past the single-pass range
-                return False
-            if (hd not in (64, 128) or ca.embed_dim > 2048 or ca.embed_dim % 8 or B > 32
-                    or p["khm"].shape[2] > decode_split_chunk(hd) or p["Wq"].stride(0) != ca.embed_dim):
+            if (cond.fp8 or hd not in (64, 128) or ca.embed_dim > 2048 or ca.embed_dim % 8 or B > 32
+                    or cond.keys > decode_split_chunk(hd) or p["Wq"].stride(0) != ca.embed_dim):
                 return False
         return True
 
@@ -548,8 +471,9 @@ class DecodeEngine:
         like its weights; the LayerNorm(+FiLM) prologues run on the packed
         rows.  9 launches per layer, as _step_rows."""
         m, c = self.m, self.ctx
+        cond = c["cond"]
         xp = None   # packed image of the residual stream (none before layer 0)
-        for i, (l, p) in enumerate(zip(m.layers, c["layers"])):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
             conv_state, ssm_state = states[i]
             mm = l.mamba
             di, N, r = mm.d_inner, mm.d_state, mm.dt_rank
@@ -564,13 +488,13 @@ class DecodeEngine:
             x, xp = ops.gemm_rows(y, p["Wout_p"], res=x, packed_out="also")
             if self.fuse_q:   # one launch: LN + q projection in the attention kernel's prologue
                 nc = l.norm_cross
-                o = attention_decode_qproj_packed(x, p["Wq"], p["bq"], nc.weight, nc.bias, nc.eps, p["khm"],
-                                                  p["vhm"], l.cross_attn.num_heads, c["kpm"])
+                o = attention_decode_qproj_packed(x, p["Wq"], p["bq"], nc.weight, nc.bias, nc.eps, cl.khm, cl.vhm,
+                                                  cl.H, cond.kpm)
             else:
                 q = ops.gemm_rows(xp, p["Wq_p"], p["bq"], ln=ln(l.norm_cross))
-                o = self._attend(q, p, l.cross_attn.num_heads, packed=True)
+                o = cond.attend(cl, q, packed=True)
             x, xp = ops.gemm_rows(o, p["Wo_p"], p["bo"], res=x, packed_out="also")
-            f = ops.gemm_rows(xp, p["W1_p"], p["b1"], "gelu", ln=ln(l.norm_ff, p["gamma_p"], p["beta_p"]),
+            f = ops.gemm_rows(xp, p["W1_p"], p["b1"], "gelu", ln=ln(l.norm_ff, cl.gamma_p, cl.beta_p),
                               packed_out="only")
             x, xp = ops.gemm_rows(f, p["W2_p"], p["b2"], res=x, packed_out="also")
         return ops.gemm_rows(xp, c["Wh_p"], c["bh"], ln=ln(m.norm_out))[:, None]
@@ -589,7 +513,7 @@ class DecodeEngine:
     # -- one step, eager -----------------------------------------------------
     def _step(self, tok, pos, states, rows=0):
         m, c = self.m, self.ctx
-        cd = c["cd"]
+        cd, cond = c["cd"], c["cond"]
         x = (F.embedding(tok, m.token_embed.weight) + F.embedding(pos, m.pos_embed.weight)[:, None]).to(cd)
         x = x.view(c["B"], -1)                                               # (B, d)
         proj = _proj_rows if (self.use_rows and cd == torch.bfloat16) else _proj_blas
@@ -597,7 +521,7 @@ class DecodeEngine:
         def mm_(x, w, b=None, act=None):   # rows > 0: the BLAS projections at that fixed row count (_proj_blas)
             return proj(x, w, b, act, rows)
         pending = None
-        for i, (l, p) in enumerate(zip(m.layers, c["layers"])):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
             conv_state, ssm_state = states[i]
             h, xs = ops.layer_norm(x if pending is None else pending, l.norm_mamba.weight, l.norm_mamba.bias,
                                    l.norm_mamba.eps, res=None if pending is None else x)
@@ -614,10 +538,10 @@ class DecodeEngine:
             h_m = mm_(y, p["Wout"])
             h, x = ops.layer_norm(h_m, l.norm_cross.weight, l.norm_cross.bias, l.norm_cross.eps, res=x)
             q = mm_(h, p["Wq"], p["bq"])
-            o = self._attend(q, p, l.cross_attn.num_heads, packed=False)
+            o = cond.attend(cl, q, packed=False)
             a = mm_(o, p["Wo"], p["bo"])
             h, x = ops.layer_norm(a, l.norm_ff.weight, l.norm_ff.bias, l.norm_ff.eps, res=x,
-                                  gamma=p["gamma"], beta=p["beta"], rows_per_group=1)
+                                  gamma=cl.gamma, beta=cl.beta, rows_per_group=1)
             pending = mm_(mm_(h, p["W1"], p["b1"], "gelu"), p["W2"], p["b2"])
         h, _ = ops.layer_norm(pending, m.norm_out.weight, m.norm_out.bias, m.norm_out.eps, res=x)
         return mm_(h, c["Wh"], c["bh"])[:, None]
@@ -662,12 +586,12 @@ class DecodeEngine:
         token shape or kv_dtype changed; every graph goes with it) and the
         static state / token / position buffers."""
         m = self.m
-        text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
         cd = m._cd()
         key = (cd, tok_shape) if kv_dtype is None else (cd, tok_shape, kv_dtype)
         B = tok_shape[0]
         if key != self.ctx_key or not _same_ctx(self.ctx_refs, self.ctx_versions, conds):
-            self.ctx = self._build_ctx(text_hidden, z_style, text_mask, ref_hidden, ref_mask, cd, kv_dtype)
+            # the split-key routing is latched here, with the context: _xpk_ok and every later step agree on it
+            self.ctx = self._build_ctx(Conditioning.from_batch(m, *conds, cd, kv_dtype, self.OPTIONS["split_keys"]))
             self.ctx_key = key
             self.ctx_refs = conds                  # strong references (see _same_ctx)
             self.ctx_versions = tuple(None if t is None else t._version for t in conds)
@@ -682,12 +606,14 @@ class DecodeEngine:
     def _latch_routing(self, B):
         """Which step runs over self.ctx at B rows, decided once per context:
         the fused-epilogue step, its packed weights, the packed activations
-        (which also makes the head-major K / V and the packed FiLM images from
-        the context's rows) and the q projection inside the attention kernel."""
+        (with the head-major K / V and the packed FiLM images they read) and
+        the q projection inside the attention kernel."""
         self.fused = self._fused_ok(self.ctx["cd"], B)
         if self.fused and self.OPTIONS["packed"]:
             self._pack_ctx()
         self.xpk = self.fused and self._xpk_ok()
+        if self.xpk:
+            self.ctx["cond"].make_packed_images()
         self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(B)
 
     def _alloc_state(self, B, dev):

@@ -6,8 +6,9 @@ reached its cap idles until the longest one is done.  A Mamba decoder keeps
 O(1) state per row, so a finished row can be handed to the next request at
 once.  DecodeSession keeps everything a request owns as one row of static
 device buffers -- its conditioning K/V over `max_keys` keys, key-padding mask,
-key count (all the split-key attention reads of a long key side), FiLM rows,
-conv / SSM states, token, position, sampler controls, history -- and replays
+key count (all the split-key attention reads of a long key side) and FiLM rows
+in the context's Conditioning (mtts/conditioning.py, whose row operations it
+uses); conv / SSM states, token, position, sampler controls, history -- and replays
 ONE captured graph of the engine's decode step plus the slot form of the
 sampler (ops.sample_tokens_slots: the history column is the row's own
 draw count, finished rows keep their tokens and their position).  Admitting a
@@ -26,9 +27,8 @@ stays reserved ("lent") until every member has been taken.
 A session opened with kv_dtype="fp8" keeps the conditioning K/V as OCP FP8
 bytes with one fp32 scale per (slot, head) -- (slots, H, max_keys, hd) uint8
 per layer and operand, a quarter of the four bf16 images a packed session
-holds -- allocated as such (no bf16 transient); an admission quantises the
-request's padded projection straight into its slot's rows over the request's
-key count, and the captured step reads them through the fp8 form of the
+holds -- allocated as such and quantised into per admission (Conditioning.idle
+/ write), and the captured step reads them through the fp8 form of the
 split-key attention (DecodeEngine.generate's kv_dtype has the definition).
 
 plan_slots() is the refill policy as a pure host function;
@@ -37,13 +37,11 @@ generate_requests() runs a queue of requests through a session by it.
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F
 
 from . import ops
-from .attn_kernels import decode_split_chunk, key_counts, quantize_kv_fp8
+from .conditioning import Conditioning
 from .decode import (DecodeEngine, _check_request, _check_vocab_ids, _check_window, _is_scalar, capture_graph,
-                     check_kv_dtype, sampler_buffers)
-from .linear import cast_weight
+                     check_kv_dtype, check_split_keys, sampler_buffers)
 
 
 def plan_slots(caps, slots, check_every, prefilled=None, samples=None):
@@ -117,48 +115,16 @@ class DecodeSession:
         self.logprobs = bool(logprobs)                      # decided here: it selects the one capture
         self.share_keys = bool(share_keys)                  # so is this: the captured step reads K/V through kv_rows
         if self.share_keys:                                 # only the split-key kernel takes a K/V row per query row
-            if not DecodeEngine.OPTIONS["split_keys"]:
-                raise ValueError("open_session: share_keys needs the split-key attention and "
-                                 "DecodeEngine.OPTIONS['split_keys'] is off")
-            for l in m.layers:
-                ck = decode_split_chunk(l.cross_attn.embed_dim // l.cross_attn.num_heads)
-                if max_keys <= ck:
-                    raise ValueError(f"open_session: share_keys needs the split-key attention and max_keys = "
-                                     f"{max_keys} is inside the single-pass range (<= {ck} keys at this head dim)")
+            check_split_keys("open_session", "share_keys", m, max_keys, f"max_keys = {max_keys}")
         self.dev = dev
-        d = m.token_embed.weight.shape[1]
         cd = self.cd = m._cd()
         P = self.P = m.pos_embed.num_embeddings
         # a private engine over a context of `slots` idle rows, routed and given its buffers by its own methods
         eng = self.eng = DecodeEngine(m, use_graph=False)
-        keep = torch.zeros(slots, max_keys, dtype=torch.bool, device=dev)
-        keep[:, 0] = True                                   # a fully masked row would give NaN
-        ds = m.layers[0].style_mlp[0].weight.shape[1]
-        if kv_dtype is None:
-            ctx = eng._build_ctx(torch.zeros(slots, max_keys, d, device=dev, dtype=cd),
-                                 torch.zeros(slots, ds, device=dev), keep, None, None, cd)
-        else:                                               # the fp8 buffers allocated as idle rows, nothing projected
-            ctx = eng._build_ctx(torch.zeros(slots, 1, d, device=dev, dtype=cd),
-                                 torch.zeros(slots, ds, device=dev), None, None, None, cd, kv_dtype, kv_keys=max_keys)
-            ctx["kpm"] = ~keep
-            ctx["kv_lens"] = torch.ones(slots, dtype=torch.int32, device=dev)
-        self.kpm = ctx["kpm"]                               # (slots, max_keys) bool, True = ignore: rewritten in place
-        # (slots,) int32 key counts the captured step's split-key attention reads: an idle slot's only key is key 0
-        self.kv_lens = ctx["kv_lens"]
-        self.kv_lens.fill_(1)
-        for l, p in zip(m.layers, ctx["layers"]):
-            ca = l.cross_attn
-            p["Wkv"] = cast_weight(ca.in_proj_weight, cd)[d:]
-            p["bkv"] = cast_weight(ca.in_proj_bias, cd)[d:]
-            for name in ("k", "v", "gamma", "beta"):        # idle rows are zero, before the latch below copies them
-                if name in p:
-                    p[name].zero_()
-        # share_keys: query row r reads the K/V, mask and count of row kv_rows[r]; identity while idle
-        self.kv_rows = torch.arange(slots, dtype=torch.int32, device=dev) if self.share_keys else None
-        if self.share_keys:
-            ctx["kv_rows"] = self.kv_rows
-        eng.ctx = ctx
-        eng._latch_routing(slots)                           # also makes khm / vhm and the packed FiLM images
+        cond = self.cond = Conditioning.idle(slots, max_keys, cd, dev, kv_dtype, eng.OPTIONS["split_keys"], share_keys)
+        self.kpm, self.kv_lens, self.kv_rows = cond.kpm, cond.kv_lens, cond.kv_rows
+        ctx = eng.ctx = eng._build_ctx(cond)
+        eng._latch_routing(slots)
         eng._alloc_state(slots, dev)
         eng.tok_buf.fill_(self.pad)
         # the batch-1 prefill runs on an engine of its own states; the context's constants are shared
@@ -332,31 +298,19 @@ class DecodeSession:
                                    "which have not been taken")
             if self.state[r] != "idle":
                 raise RuntimeError(f"{who}: slot {r} holds a request that has not been taken")
-        # -- conditioning: [ref ‖ text] padded to max_keys, projected once, written in place: into rows[0] alone in
-        # a share_keys session (every member reads it through kv_rows), into every member's rows otherwise
+        # -- conditioning: [ref ‖ text] padded to max_keys, projected once, written into rows[0] and copied from it
         cd, K = self.cd, self.max_keys
         th, tm = m._concat_ref(th.to(cd), tm, rh, rm, 1, dev)
         thp = torch.zeros(1, K, d, device=dev, dtype=cd)
         thp[:, :S] = th
         keep = torch.zeros(1, K, dtype=torch.bool, device=dev)
         keep[:, :S] = True if tm is None else tm.to(dev)
-        kv_to = rows[:1] if self.share_keys else rows
-        counts = key_counts(keep)                           # as generate() derives it from the same mask
-        for r in kv_to:
-            self.kpm[r] = ~keep[0]
-            self.kv_lens[r:r + 1].copy_(counts)
-        for l, p in zip(m.layers, eng.ctx["layers"]):
-            kv = torch.addmm(p["bkv"], thp.reshape(-1, d), p["Wkv"].t())           # (max_keys, 2d): one shape, always
-            lin = l.style_mlp[0]
-            gb = torch.tanh(F.linear(z.to(lin.weight.dtype), lin.weight, lin.bias)).to(cd)
-            for r in kv_to:                                 # FP8 keys: quantised once, the other members get the bytes
-                self._write_kv(p, r, kv[:, :d], kv[:, d:], l.cross_attn.num_heads, counts,
-                               like=None if r == kv_to[0] else kv_to[0])
-            for r in rows:
-                self._write_film(p, r, gb[0, :d], gb[0, d:])
+        self.cond.write(rows[0], thp, keep, z)
+        for r in rows[1:]:                                  # FP8 keys: quantised once, the other members get the bytes
+            self.cond.copy(rows[0], r, keys=not self.share_keys)
         if self.share_keys:
             for r in rows:
-                self.kv_rows[r:r + 1].fill_(rows[0])
+                self.cond.point(r, rows[0])
                 self.holder[r] = rows[0]
             self.borrowers[rows[0]] = set(rows[1:])
         logits0 = None
@@ -391,55 +345,9 @@ class DecodeSession:
                 eng.pos_buf[r:r + 1].zero_()
             self.state[r] = "live"
 
-    def _write_kv(self, p, r, k, v, H, counts, like=None):
-        """Row r of one layer's K / V (and head-major copies), in place.  k, v
-        (max_keys, d).  FP8 keys: quantised straight into the slot's rows over
-        the request's key count `counts` ((1,) int32 on the device); the
-        bytes past it are zero.  like: a slot already written with these very
-        k, v and counts (an earlier member of an admit_samples group), whose
-        bytes and scales are copied instead."""
-        K, d = k.shape
-        if "k8" in p and like is not None:
-            for name in ("k8", "v8", "k_scale", "v_scale"):
-                p[name][r].copy_(p[name][like])
-            return
-        if "k8" in p:
-            quantize_kv_fp8(k[None], H, counts, out=p["k8"][r:r + 1], scale_out=p["k_scale"][r:r + 1])
-            quantize_kv_fp8(v[None], H, counts, out=p["v8"][r:r + 1], scale_out=p["v_scale"][r:r + 1])
-            return
-        p["k"][r].copy_(k)
-        p["v"][r].copy_(v)
-        if "khm" in p:
-            p["khm"][r].copy_(k.reshape(K, H, d // H).permute(1, 0, 2))
-            p["vhm"][r].copy_(v.reshape(K, H, d // H).permute(1, 0, 2))
-
-    def _write_film(self, p, r, gamma, beta):
-        """Row r of one layer's FiLM rows (and packed images), in place.  gamma, beta (d,)."""
-        d = gamma.shape[0]
-        p["gamma"][r].copy_(gamma)
-        p["beta"][r].copy_(beta)
-        if "gamma_p" in p:                                  # PackedAct.pack's layout: [s, half, g, row, q]
-            for name, row in (("gamma_p", gamma), ("beta_p", beta)):
-                img = p[name].data.view(d // 32, 2, 4, 16, 8)
-                img[:, r // 16, :, r % 16, :].copy_(row.reshape(d // 32, 4, 8))
-
     def _make_idle(self, r):
         eng = self.eng
-        z = torch.zeros((), device=self.dev, dtype=self.cd)
-        for l, p in zip(self.m.layers, eng.ctx["layers"]):
-            d = p["gamma"].shape[1]
-            if "k8" in p:                                   # zero bytes and scale 1
-                for name, fill in (("k8", 0), ("v8", 0), ("k_scale", 1.0), ("v_scale", 1.0)):
-                    p[name][r].fill_(fill)
-            else:
-                K = p["k"].shape[1]
-                self._write_kv(p, r, z.expand(K, d), z.expand(K, d), l.cross_attn.num_heads, None)
-            self._write_film(p, r, z.expand(d), z.expand(d))
-        self.kpm[r] = True
-        self.kpm[r, 0] = False
-        self.kv_lens[r:r + 1].fill_(1)
-        if self.kv_rows is not None:                        # a borrower reads its own (idle) rows again
-            self.kv_rows[r:r + 1].fill_(r)
+        self.cond.clear(r)                                  # a borrower reads its own (idle) rows again
         self.holder[r] = r
         self.finished[r:r + 1].fill_(1)
         eng.tok_buf[r].fill_(self.pad)

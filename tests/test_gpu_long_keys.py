@@ -69,13 +69,13 @@ def test_long_keys_keep_the_packed_step(model, monkeypatch):
     from mtts.decode import DecodeEngine
     assert DecodeEngine.OPTIONS["split_keys"] is True
     ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert ses.eng.fused and ses.eng.xpk and "khm" in ses.eng.ctx["layers"][0]
-    assert ses.eng.ctx["kv_lens"] is ses.kv_lens and ses.kv_lens.dtype == torch.int32
+    assert ses.eng.fused and ses.eng.xpk and ses.cond.layers[0].khm is not None
+    assert ses.eng.ctx["cond"].kv_lens is ses.kv_lens and ses.kv_lens.dtype == torch.int32
     assert ses.kv_lens.tolist() == [1] * SLOTS              # an idle slot's only key is key 0
     assert not ses.eng.fuse_q
     monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", False)
     old = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert old.eng.fused and not old.eng.xpk and "khm" not in old.eng.ctx["layers"][0]
+    assert old.eng.fused and not old.eng.xpk and old.cond.layers[0].khm is None
 
 
 def _conds():
@@ -110,7 +110,7 @@ def test_bf16_step_matches_the_module_path(model, mode):
     try:
         got = _six_steps(model, mode, text, z, mask, tok)
         eng = model._engine
-        assert eng.fused and eng.xpk and eng.ctx["kv_lens"].tolist() == [KEYS, 300, CK + 1]
+        assert eng.fused and eng.xpk and eng.ctx["cond"].kv_lens.tolist() == [KEYS, 300, CK + 1]
         want = _six_steps(model, None, text, z, mask, tok)
     finally:
         model.decode_mode = "graph"
@@ -128,7 +128,7 @@ def test_fp32_step_matches_the_module_path(mode):
     m = _decoder(None)
     text, z, mask, tok = _conds()
     got = _six_steps(m, mode, text, z, mask, tok)
-    assert not m._engine.fused and m._engine.ctx["kv_lens"].tolist() == [KEYS, 300, CK + 1]
+    assert not m._engine.fused and m._engine.ctx["cond"].kv_lens.tolist() == [KEYS, 300, CK + 1]
     want = _six_steps(m, None, text, z, mask, tok)
     err = (got - want).abs().max().item() / want.abs().max().item()
     print(f"fp32 engine ({mode}) vs module path at {KEYS} keys: {err:.3e} of the logit scale")
@@ -166,11 +166,11 @@ def test_stale_keys_do_not_leak(model):
     _solo(ses, 2, _req(KEYS, 4, cap=9))
     ses.admit(2, **req)
     assert ses.kv_lens[2].item() == 5
-    for p in ses.eng.ctx["layers"]:                         # what the slot's rows hold past the request's keys
-        p["k"][2, 5:] = float("nan")
-        p["v"][2, 5:] = float("nan")
-        p["khm"][2, :, 5:] = float("nan")
-        p["vhm"][2, :, 5:] = float("nan")
+    for p in ses.cond.layers:                               # what the slot's rows hold past the request's keys
+        p.k[2, 5:] = float("nan")
+        p.v[2, 5:] = float("nan")
+        p.khm[2, :, 5:] = float("nan")
+        p.vhm[2, :, 5:] = float("nan")
     ses.run(CAP)
     assert 2 in ses.poll()
     assert torch.equal(ses.take(2), want)
@@ -203,14 +203,14 @@ def test_routing_is_fixed_when_the_context_is_built(model, monkeypatch):
     model.decode_mode = "eager"
     try:
         ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-        assert ses.captures == 0 and ses.eng.xpk and ses.eng.ctx["split"] is True
+        assert ses.captures == 0 and ses.eng.xpk and ses.cond.split is True
         want = _solo(ses, 1, req)
         monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", False)
         assert torch.equal(_solo(ses, 1, req), want)        # still the packed step on the split kernel
         old = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-        assert not old.eng.xpk and old.eng.ctx["split"] is False
+        assert not old.eng.xpk and old.cond.split is False
         monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", True)
         assert _solo(old, 1, req).shape == (CAP,)           # still the parent's routing: no packed call is made
-        assert old.eng.ctx["split_ws"] is None and ses.eng.ctx["split_ws"] is not None
+        assert old.cond.split_ws is None and ses.cond.split_ws is not None
     finally:
         model.decode_mode = "graph"

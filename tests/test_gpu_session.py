@@ -129,8 +129,8 @@ def test_packed_step_slots_in_both_halves_of_the_image():
 
     r0, r1, r2 = req(0, 20), req(1, 30), req(2, 30)
     ses = m.open_session(20, KEYS, repetition_window=WINDOW)
-    assert ses.eng.xpk and "khm" in ses.eng.ctx["layers"][0] and "gamma_p" in ses.eng.ctx["layers"][0]
-    packed = ses.eng.ctx["layers"][0]["gamma_p"].data
+    assert ses.eng.xpk and ses.cond.layers[0].khm is not None and ses.cond.layers[0].gamma_p is not None
+    packed = ses.cond.layers[0].gamma_p.data
     want = _solo(ses, 1, r0)
     assert len(torch.unique(want)) > 3
     ses.admit(0, **r1)
@@ -138,7 +138,7 @@ def test_packed_step_slots_in_both_halves_of_the_image():
     ses.run(7)
     assert torch.equal(_solo(ses, 17, r0), want)            # the second half of the image, with neighbours
     assert torch.equal(_solo(ses, 1, r0), want)
-    assert ses.eng.ctx["layers"][0]["gamma_p"].data is packed and ses.captures == 1
+    assert ses.cond.layers[0].gamma_p.data is packed and ses.captures == 1
     text = torch.zeros(1, KEYS, dm, device=DEV)
     text[0, :LENS[0]] = r0["text_hidden"]
     mask = torch.zeros(1, KEYS, dtype=torch.bool, device=DEV)
@@ -227,8 +227,8 @@ def test_eos_ends_a_request_before_its_cap():
 def _snapshot(ses):
     out = [ses.kpm, ses.finished, ses.length, ses.eng.tok_buf, ses.eng.pos32, ses.eng.pos_buf]
     out += list(ses.g.values())
-    for p in ses.eng.ctx["layers"]:
-        out += [p["k"], p["v"], p["gamma"], p["beta"]]
+    for p in ses.cond.layers:
+        out += [p.k, p.v, p.gamma, p.beta]
     for cs, ss in ses.eng.states:
         out += [cs, ss]
     return [t.clone() for t in out], out

@@ -100,8 +100,8 @@ def test_stale_keys_do_not_leak(model):
     assert ses.kv_lens[1].item() == 1
     ses.admit(1, **req)
     assert ses.kv_lens[1].item() == 5
-    for p in ses.eng.ctx["layers"]:
-        assert (p["k8"][1, :, 5:] == 0).all() and (p["v8"][1, :, 5:] == 0).all()
+    for p in ses.cond.layers:
+        assert (p.k8[1, :, 5:] == 0).all() and (p.v8[1, :, 5:] == 0).all()
     ses.run(CAP)
     assert 1 in ses.poll()
     assert _same(ses.take(1, return_logprobs=True), want)
@@ -127,21 +127,21 @@ def test_the_session_holds_fp8_keys_and_no_bf16_image(model):
     model.decode_mode = "graph"
     ses = _open(model)
     assert ses.captures == 1 and ses.eng.fused and ses.eng.xpk and not ses.eng.fuse_q
-    for p in ses.eng.ctx["layers"]:
-        for name in ("k8", "v8"):
-            assert p[name].shape == (SLOTS, HEADS, KEYS, HD) and p[name].dtype == torch.uint8
-            assert p[name].is_contiguous() and (p[name] == 0).all()
-        for name in ("k_scale", "v_scale"):
-            assert p[name].shape == (SLOTS, HEADS) and p[name].dtype == torch.float32 and (p[name] == 1).all()
-        assert not any(name in p for name in ("k", "v", "khm", "vhm"))
+    for p in ses.cond.layers:
+        for t in (p.k8, p.v8):
+            assert t.shape == (SLOTS, HEADS, KEYS, HD) and t.dtype == torch.uint8
+            assert t.is_contiguous() and (t == 0).all()
+        for t in (p.k_scale, p.v_scale):
+            assert t.shape == (SLOTS, HEADS) and t.dtype == torch.float32 and (t == 1).all()
+        assert all(t is None for t in (p.k, p.v, p.khm, p.vhm))
     ses.admit(2, **_req(300, 1))
-    p = ses.eng.ctx["layers"][0]
-    assert (p["k8"][2, :, :300] != 0).any() and (p["k8"][2, :, 300:] == 0).all() and (p["k_scale"][2] != 1).all()
-    assert (p["k8"][[0, 1, 3]] == 0).all() and (p["k_scale"][[0, 1, 3]] == 1).all()
+    p = ses.cond.layers[0]
+    assert (p.k8[2, :, :300] != 0).any() and (p.k8[2, :, 300:] == 0).all() and (p.k_scale[2] != 1).all()
+    assert (p.k8[[0, 1, 3]] == 0).all() and (p.k_scale[[0, 1, 3]] == 1).all()
     ses.run(CAP)
     ses.take(2)
-    assert (p["k8"][2] == 0).all() and (p["v8"][2] == 0).all()         # idle again: zero bytes, scale 1
-    assert (p["k_scale"][2] == 1).all() and (p["v_scale"][2] == 1).all()
+    assert (p.k8[2] == 0).all() and (p.v8[2] == 0).all()               # idle again: zero bytes, scale 1
+    assert (p.k_scale[2] == 1).all() and (p.v_scale[2] == 1).all()
 
 
 def test_generate_keeps_fp8_keys_and_rebuilds_on_a_change(model):
@@ -150,13 +150,13 @@ def test_generate_keeps_fp8_keys_and_rebuilds_on_a_change(model):
     a, _ = model.generate(text, z, 4, kv_dtype="fp8")
     eng = model._engine
     ctx = eng.ctx
-    assert all("k8" in p and not any(n in p for n in ("k", "v", "khm", "vhm")) for p in ctx["layers"])
-    assert ctx["layers"][0]["k8"].shape == (2, HEADS, KEYS, HD) and eng.ctx_key[-1] == "fp8"
+    assert all(p.k8 is not None and all(t is None for t in (p.k, p.v, p.khm, p.vhm)) for p in ctx["cond"].layers)
+    assert ctx["cond"].layers[0].k8.shape == (2, HEADS, KEYS, HD) and eng.ctx_key[-1] == "fp8"
     assert eng.fused and eng.xpk and not eng.fuse_q
     again, _ = model.generate(text, z, 4, kv_dtype="fp8")
     assert eng.ctx is ctx and torch.equal(again, a)         # the same tensors and value: the context is kept
     b, _ = model.generate(text, z, 4)                       # the same tensors, kv_dtype off: a new context
-    assert eng.ctx is not ctx and "k" in eng.ctx["layers"][0] and "k8" not in eng.ctx["layers"][0]
+    assert eng.ctx is not ctx and eng.ctx["cond"].layers[0].k is not None and eng.ctx["cond"].layers[0].k8 is None
     assert len(eng.ctx_key) == 2 and a.shape == b.shape
 
 

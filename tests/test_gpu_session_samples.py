@@ -75,7 +75,7 @@ def test_members_equal_admit_alone(model, prompt):
         if share:
             assert ses.kv_rows.tolist() == [3, 1, 3, 3]
             assert ses.kv_lens.tolist() == [1, 40, 1, KEYS - 3]
-            k = ses.eng.ctx["layers"][0]["k"]
+            k = ses.cond.layers[0].k
             assert not k[0].any() and not k[2].any() and k[3].any()             # one copy of the keys
         else:
             assert ses.kv_rows is None and ses.kv_lens.tolist() == [KEYS - 3, 40, KEYS - 3, KEYS - 3]
@@ -109,7 +109,7 @@ def test_the_slot_that_holds_the_keys_stays_reserved(model):
     assert "live" in ses.state
     assert torch.equal(ses.take(3), refs[0])                 # the holder first
     assert ses.state[3] == "lent" and ses.kv_rows.tolist() == [3, 1, 3, 3]
-    assert ses.eng.ctx["layers"][0]["k"][3].any()            # its rows are still there for the others
+    assert ses.cond.layers[0].k[3].any()            # its rows are still there for the others
     with pytest.raises(RuntimeError, match="slot 3"):
         ses.admit(3, seed=1, **other)
     with pytest.raises(RuntimeError, match="slot 3"):
@@ -124,7 +124,7 @@ def test_the_slot_that_holds_the_keys_stays_reserved(model):
         ses.admit(3, seed=1, **other)
     assert torch.equal(ses.take(2), refs[2])
     assert ses.state == ["idle"] * SLOTS and _identity(ses)
-    assert not ses.eng.ctx["layers"][0]["k"][3].any() and ses.kv_lens.tolist() == [1] * SLOTS
+    assert not ses.cond.layers[0].k[3].any() and ses.kv_lens.tolist() == [1] * SLOTS
     ses.admit(3, seed=1, **other)                            # and now it is a slot like any other
     _run_out(ses)
     assert torch.equal(ses.take(3), _alone(plain, other, 1)[0])
@@ -135,7 +135,7 @@ def test_checks_come_before_any_write(model):
     ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW, share_keys=True)
     req = _req(20, 5)
     ses.admit(2, seed=1, **req)
-    before = ses.eng.ctx["layers"][0]["k"].clone()
+    before = ses.cond.layers[0].k.clone()
     with pytest.raises(RuntimeError, match="slot 2"):
         ses.admit_samples([0, 2], seed=1, **req)
     with pytest.raises(ValueError):
@@ -147,7 +147,7 @@ def test_checks_come_before_any_write(model):
     with pytest.raises(ValueError):
         ses.admit_samples([0, SLOTS], seed=1, **req)
     assert ses.state == ["idle", "idle", "live", "idle"] and _identity(ses)
-    assert torch.equal(ses.eng.ctx["layers"][0]["k"], before) and ses.kv_lens.tolist() == [1, 1, 20, 1]
+    assert torch.equal(ses.cond.layers[0].k, before) and ses.kv_lens.tolist() == [1, 1, 20, 1]
 
 
 def test_share_keys_needs_the_split_key_routing(model, monkeypatch):

@@ -338,7 +338,6 @@ def kv_fp8_leg(n, dev, lines):
                  "session (bf16: k, v and the head-major copies; fp8: bytes and scales)")
     shapes = (("train.py widths (8L d=512 8 heads)", dict(n_layers=8, d_model=512, n_heads=8), 5248, (1, 8, 32)),
               ("C4 widths (12L d=1024 8 heads)", dict(n_layers=12, d_model=1024, n_heads=8), 1024, (32,)))
-    names = ("k", "v", "khm", "vhm", "k8", "v8", "k_scale", "v_scale")
 
     def fmt(v):
         return f"{statistics.median(v):8.1f} [{min(v):.1f} {max(v):.1f}]  spread {max(v) - min(v):.1f}"
@@ -356,8 +355,7 @@ def kv_fp8_leg(n, dev, lines):
             ses = {"b": m.open_session(slots, max_keys, repetition_window=64),
                    "f": m.open_session(slots, max_keys, repetition_window=64, kv_dtype="fp8")}
             assert ses["b"].eng.xpk and ses["f"].eng.xpk
-            held = {leg: sum(p[k].numel() * p[k].element_size() for p in s.eng.ctx["layers"] for k in names if k in p)
-                    for leg, s in ses.items()}
+            held = {leg: s.cond.kv_bytes() for leg, s in ses.items()}
             kw = dict(temperature=1.0, top_k=50, top_p=0.9)
 
             def run(leg, ragged):
