@@ -24,8 +24,8 @@ class Conditioning:
     style nn.Linear) and the images, None where one does not exist: k / v
     (column views of one (rows, keys, 2d) projection), khm / vhm / gamma_p /
     beta_p of a packed step, or -- "fp8" -- k8 / v8 e4m3fn bytes (rows, H,
-    keys, hd) with k_scale / v_scale (rows, H) and no bf16 image.  _build_ctx
-    adds the layers beside the model's constants: one cast order."""
+    keys, hd) with k_scale / v_scale (rows, H) and no bf16 image.  DecodeContext
+    (mtts/context.py) adds the layers beside the model's constants: one cast order."""
 
     def __init__(self, rows, keys, cd, kv_dtype, split, kpm, kv_lens, kv_rows=None, source=None):
         self.rows, self.keys, self.cd, self.fp8, self.split = rows, keys, cd, kv_dtype == "fp8", bool(split)

@@ -5,8 +5,9 @@ quant_embed, pos = step_index), runs every layer with its Mamba state and
 cross-attends to [ref ‖ text].  The reference recomputes, every step, the
 K/V projections of the (constant) conditioning sequence and the FiLM
 gamma/beta of the (constant) style vector; the engine computes them once per
-context and keeps them in HBM (ctx["cond"], the Conditioning of mtts/conditioning.py,
-beside the model's cast constants ctx["layers"]) with the per-layer SSM/conv state.
+context and keeps them in HBM (ctx.cond, the Conditioning of mtts/conditioning.py,
+held by the model's cast constants, the DecodeContext of mtts/context.py, which
+also decides which step runs) with the per-layer SSM/conv state.
 
 Engine path (inference only: torch.no_grad, HIP tensors):
   * context cache keyed on the object identity (strong references are
@@ -55,7 +56,8 @@ from . import ops
 from .embed import _err_flag, embed_sum
 from .attn_kernels import attention_decode_qproj_packed, decode_split_chunk
 from .conditioning import Conditioning
-from .linear import cast_scope, cast_weight
+from .context import DecodeContext
+from .linear import cast_scope
 
 
 def _same_ctx(refs, versions, tensors):
@@ -293,68 +295,44 @@ class DecodeEngine:
         self._err_host = None
         self._err_ev = None
         self._err_dev = None
-        self.xpk = False
-        self.fuse_q = False
-        self.ctx_key = None
-        self.ctx_refs = None
-        self.ctx_versions = None
-        self.ctx = None
-        self.graph = None
-        self.gen_graphs = {}
-        self.gen = None
-        self.states = None
+        self.drop()
         if flagged:
             raise IndexError("decode_step: last_token id out of range of token_embed (index out of range in self)")
 
-    # -- conditioning context -------------------------------------------------
-    def _build_ctx(self, cond):
-        """The context over `cond` (Conditioning.from_batch or .idle), whose layers are added here."""
-        m = self.m
-        cd = cond.cd
-        d = m.token_embed.weight.shape[1]
-        dev = m.token_embed.weight.device
-        layers = []
-        for l in m.layers:
-            ca = l.cross_attn
-            W = cast_weight(ca.in_proj_weight, cd)
-            b = cast_weight(ca.in_proj_bias, cd)
-            cond.add_layer(l, W[d:], b[d:])
-            mm = l.mamba
-            di = mm.d_inner
-            layers.append(dict(
-                Wq=W[:d], bq=b[:d], Wo=cast_weight(ca.out_proj.weight, cd), bo=cast_weight(ca.out_proj.bias, cd),
-                W1=cast_weight(l.ff[0].weight, cd), b1=cast_weight(l.ff[0].bias, cd),
-                W2=cast_weight(l.ff[2].weight, cd), b2=cast_weight(l.ff[2].bias, cd),
-                Win=cast_weight(mm.in_proj.weight, cd), Wx=cast_weight(mm.x_proj.weight, cd),
-                Wdt=cast_weight(mm.dt_proj.weight, cd), Wout=cast_weight(mm.out_proj.weight, cd),
-                conv_w=mm.conv1d.weight.detach().reshape(di, -1).float().contiguous(),
-                conv_b=mm.conv1d.bias.detach().float().contiguous(),
-                A=(-torch.exp(mm.A_log.detach().float())).contiguous(), D=mm.D.detach().float().contiguous(),
-                dt_bias=mm.dt_proj.bias.detach().float().contiguous(),
-            ))
-        cond.source = None
-        return dict(B=cond.rows, cond=cond, layers=layers, cd=cd,
-                    tok_w=m.token_embed.weight.detach().float().contiguous(),
-                    pos_w=m.pos_embed.weight.detach().float().contiguous(),
-                    q0_w=torch.zeros(1, d, device=dev), q0_id=torch.zeros(1, device=dev, dtype=torch.int32),
-                    Wh=cast_weight(m.head.weight, cd), bh=cast_weight(m.head.bias, cd))
+    # -- the context and what lives as long as it does ----------------------------
+    def drop(self):
+        """No context: everything whose lifetime is the context's, declared here and nowhere else."""
+        self.ctx = None                                     # the DecodeContext (adopt)
+        self.ctx_key = self.ctx_refs = self.ctx_versions = None     # what _prepare built it from
+        self.states = self.tok_buf = self.pos_buf = self.pos32 = None   # the static buffers (adopt)
+        self.graph = self.out_buf = None                    # decode_step's capture and its static output
+        self.gen_graphs = {}                                # generate's captures, its buffers, its prefill's logits
+        self.gen = self.prefill_logits = None
 
-    def _fused_ok(self, cd, B):
-        """The fused-epilogue step (_step_rows) applies: bf16, <= 32 rows and
-        the shapes csrc/rows.hip takes (checked once per context)."""
-        m = self.m
-        if (not self.use_rows or cd != torch.bfloat16 or B > ops.GEMM_ROWS_MAX
-                or not self.OPTIONS["fused"]):
-            return False
-        d = m.token_embed.weight.shape[1]
-        if not ops.gemm_rows_ln_ok(d):
-            return False
-        for l in m.layers:
-            mm = l.mamba
-            if (mm.d_conv != 4 or d % 64 or mm.d_inner % 64 or d % 8 or d > 2048 or l.ff[0].weight.shape[0] % 64
-                    or any(n.weight.dtype != torch.float32 for n in (l.norm_mamba, l.norm_cross, l.norm_ff))):
-                return False
-        return m.norm_out.weight.dtype == torch.float32
+    def adopt(self, ctx, rows, dev):
+        """`ctx` (DecodeContext.build) as the engine's context, with the static per-layer (conv, SSM) states and
+        token / position buffers of `rows` rows, zeroed.  A session's prefill engine adopts the stepping
+        engine's context at 1 row: the constants and the routing are shared, the states are its own."""
+        self.ctx = ctx
+        self.states = [(torch.zeros(rows, l.mamba.d_inner, l.mamba.d_conv, device=dev),
+                        torch.zeros(rows, l.mamba.d_inner, l.mamba.d_state, device=dev)) for l in self.m.layers]
+        self.tok_buf = torch.zeros(rows, 1, dtype=torch.long, device=dev)
+        # per-row positions: int64 for the eager step's F.embedding, int32 for the fused step
+        self.pos_buf = torch.zeros(rows, dtype=torch.long, device=dev)
+        self.pos32 = torch.zeros(rows, dtype=torch.int32, device=dev)
+
+    @property
+    def step_pos(self):
+        """The position buffer the step reads: the fused step embeds int32 position ids."""
+        return self.pos32 if self.ctx.fused else self.pos_buf
+
+    def set_pos(self, value, rows=slice(None)):
+        """Both position buffers, on `rows`, from an int or a tensor."""
+        for buf in (self.pos32, self.pos_buf):
+            if isinstance(value, torch.Tensor):
+                buf[rows].copy_(value)
+            else:
+                buf[rows].fill_(value)
 
     def _embed(self, tok):
         """token_embed(last_token) + pos_embed(step_index) in the compute dtype
@@ -363,28 +341,14 @@ class DecodeEngine:
         from the (B,) int32 buffer pos32) instead of two gathers, an add and a
         cast."""
         m, c = self.m, self.ctx
-        B = c["B"]
+        B = c.rows
         d = m.token_embed.weight.shape[1]
-        out = torch.empty(B, d, device=tok.device, dtype=c["cd"])
-        tw, pw = c["tok_w"], c["pos_w"]
-        L.call_raw("mtts_embed_sum_at", tok.data_ptr(), tok.stride(0), c["q0_id"].data_ptr(), self.pos32.data_ptr(),
-                   tw.data_ptr(), c["q0_w"].data_ptr(), pw.data_ptr(), B, 1, d, tw.shape[0], out.data_ptr(),
+        out = torch.empty(B, d, device=tok.device, dtype=c.cd)
+        tw, pw = c.tok_w, c.pos_w
+        L.call_raw("mtts_embed_sum_at", tok.data_ptr(), tok.stride(0), c.q0_id.data_ptr(), self.pos32.data_ptr(),
+                   tw.data_ptr(), c.q0_w.data_ptr(), pw.data_ptr(), B, 1, d, tw.shape[0], out.data_ptr(),
                    L.dtype_code(out), out.stride(0), _err_flag(tok.device).data_ptr(), 1, pw.shape[0])
         return out
-
-    _PACKED = ("Win", "Wx", "Wout", "Wq", "Wo", "W1", "W2")
-
-    def _pack_ctx(self):
-        """Packed (MFMA-fragment order) images of the step's projection
-        weights for csrc/gemv.hip, made once per context; shapes the packed
-        kernel does not take keep the row-major weight."""
-        c = self.ctx
-        for p in c["layers"]:
-            for k in self._PACKED:
-                if ops.gemv_split_ok(p[k].shape[1], ln=k in ("Win", "Wq", "W1")):
-                    p[k + "_p"] = ops.pack_rows_weight(p[k])
-        if ops.gemv_split_ok(c["Wh"].shape[1], ln=True):
-            c["Wh_p"] = ops.pack_rows_weight(c["Wh"])
 
     # -- one step, fused epilogues (bf16, <= 32 sequences) ---------------------
     def _step_rows(self, tok, pos, states):
@@ -396,70 +360,36 @@ class DecodeEngine:
         x is the bf16 residual stream, exactly as the LayerNorm kernels'
         x_sum of the generic step."""
         m, c = self.m, self.ctx
-        cond = c["cond"]
+        cond = c.cond
         x = self._embed(tok)
 
         def ln(norm, gamma=None, beta=None):
             return (norm.weight, norm.bias, norm.eps, gamma, beta)
 
-        def w(p, k):   # packed image when there is one (csrc/gemv.hip)
-            return p.get(k + "_p", p[k])
-
-        if self.xpk:
+        if c.xpk:
             return self._step_xpk(x, states, ln)
 
         fuse_conv = self.OPTIONS["fuse_conv"]
-        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c.layers, cond.layers)):
             conv_state, ssm_state = states[i]
             mm = l.mamba
             di, N, r = mm.d_inner, mm.d_state, mm.dt_rank
             if fuse_conv:
-                xz, u = ops.gemm_rows(x, w(p, "Win"), conv=(conv_state, p["conv_w"], p["conv_b"]),
+                xz, u = ops.gemm_rows(x, p.Win.operand, conv=(conv_state, p.conv_w, p.conv_b),
                                       ln=ln(l.norm_mamba))
             else:
-                xz = ops.gemm_rows(x, w(p, "Win"), ln=ln(l.norm_mamba))
-                u = ops.conv_update(xz[:, :di], conv_state, p["conv_w"], p["conv_b"], True)
-            x_dbl = ops.gemm_rows(u, w(p, "Wx"))
-            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p["A"], x_dbl[:, r:r + N], x_dbl[:, r + N:], p["D"],
-                                 xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"])
-            x = ops.gemm_rows(y, w(p, "Wout"), res=x)
-            q = ops.gemm_rows(x, w(p, "Wq"), p["bq"], ln=ln(l.norm_cross))
+                xz = ops.gemm_rows(x, p.Win.operand, ln=ln(l.norm_mamba))
+                u = ops.conv_update(xz[:, :di], conv_state, p.conv_w, p.conv_b, True)
+            x_dbl = ops.gemm_rows(u, p.Wx.operand)
+            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p.A, x_dbl[:, r:r + N], x_dbl[:, r + N:], p.D,
+                                 xz[:, di:], p.dt_bias, True, dt_w=p.Wdt)
+            x = ops.gemm_rows(y, p.Wout.operand, res=x)
+            q = ops.gemm_rows(x, p.Wq.operand, p.bq, ln=ln(l.norm_cross))
             o = cond.attend(cl, q, packed=False)
-            x = ops.gemm_rows(o, w(p, "Wo"), p["bo"], res=x)
-            f = ops.gemm_rows(x, w(p, "W1"), p["b1"], "gelu", ln=ln(l.norm_ff, cl.gamma, cl.beta))
-            x = ops.gemm_rows(f, w(p, "W2"), p["b2"], res=x)
-        return ops.gemm_rows(x, w(c, "Wh"), c["bh"], ln=ln(m.norm_out))[:, None]
-
-    def _xpk_ok(self):
-        """Every projection packed and every operand shape the packed
-        activation images take (K, N % 32; a key side the single-pass or the
-        split-key kernel takes): the step of _step_xpk applies; makes nothing."""
-        if not self.OPTIONS["xpacked"]:
-            return False
-        c = self.ctx
-        names = self._PACKED
-        if not all(k + "_p" in p for p in c["layers"] for k in names) or "Wh_p" not in c:
-            return False
-        for l, p in zip(self.m.layers, c["layers"]):
-            ca = l.cross_attn
-            hd = ca.embed_dim // ca.num_heads
-            if (any(p[k].shape[0] % 32 or p[k].shape[1] % 32 for k in names)
-                    or (c["cond"].keys > decode_split_chunk(hd) and not c["cond"].splits(hd))
-                    or l.mamba.d_inner % 32):
-                return False
-        return True
-
-    def _fuse_q_ok(self, B):
-        """Shapes mtts_attention_decode_qproj takes (head_dim 64 / 128,
-        d_model <= 2048, <= 32 sequences, no FP8 keys, the single-pass range)."""
-        cond = self.ctx["cond"]
-        for l, p in zip(self.m.layers, self.ctx["layers"]):
-            ca = l.cross_attn
-            hd = ca.embed_dim // ca.num_heads
-            if (cond.fp8 or hd not in (64, 128) or ca.embed_dim > 2048 or ca.embed_dim % 8 or B > 32
-                    or cond.keys > decode_split_chunk(hd) or p["Wq"].stride(0) != ca.embed_dim):
-                return False
-        return True
+            x = ops.gemm_rows(o, p.Wo.operand, p.bo, res=x)
+            f = ops.gemm_rows(x, p.W1.operand, p.b1, "gelu", ln=ln(l.norm_ff, cl.gamma, cl.beta))
+            x = ops.gemm_rows(f, p.W2.operand, p.b2, res=x)
+        return ops.gemm_rows(x, c.Wh.operand, c.bh, ln=ln(m.norm_out))[:, None]
 
     def _step_xpk(self, x, states, ln):
         """_step_rows with packed activations (csrc/gemv.hip, common.h
@@ -471,40 +401,40 @@ class DecodeEngine:
         like its weights; the LayerNorm(+FiLM) prologues run on the packed
         rows.  9 launches per layer, as _step_rows."""
         m, c = self.m, self.ctx
-        cond = c["cond"]
+        cond = c.cond
         xp = None   # packed image of the residual stream (none before layer 0)
-        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c.layers, cond.layers)):
             conv_state, ssm_state = states[i]
             mm = l.mamba
             di, N, r = mm.d_inner, mm.d_state, mm.dt_rank
-            xz, u, up = ops.gemm_rows(x if xp is None else xp, p["Win_p"],
-                                      conv=(conv_state, p["conv_w"], p["conv_b"]), ln=ln(l.norm_mamba),
+            xz, u, up = ops.gemm_rows(x if xp is None else xp, p.Win.packed,
+                                      conv=(conv_state, p.conv_w, p.conv_b), ln=ln(l.norm_mamba),
                                       u_packed=True)
             # (x_proj fused into the state update measured slower, 1.10 vs 0.77 ms
             # per step: every workgroup pulls 512 KiB through dependent L2 trips)
-            x_dbl = ops.gemm_rows(up, p["Wx_p"])
-            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p["A"], x_dbl[:, r:r + N], x_dbl[:, r + N:], p["D"],
-                                 xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"], packed_out=True)
-            x, xp = ops.gemm_rows(y, p["Wout_p"], res=x, packed_out="also")
-            if self.fuse_q:   # one launch: LN + q projection in the attention kernel's prologue
+            x_dbl = ops.gemm_rows(up, p.Wx.packed)
+            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p.A, x_dbl[:, r:r + N], x_dbl[:, r + N:], p.D,
+                                 xz[:, di:], p.dt_bias, True, dt_w=p.Wdt, packed_out=True)
+            x, xp = ops.gemm_rows(y, p.Wout.packed, res=x, packed_out="also")
+            if c.fuse_q:   # one launch: LN + q projection in the attention kernel's prologue
                 nc = l.norm_cross
-                o = attention_decode_qproj_packed(x, p["Wq"], p["bq"], nc.weight, nc.bias, nc.eps, cl.khm, cl.vhm,
+                o = attention_decode_qproj_packed(x, p.Wq.w, p.bq, nc.weight, nc.bias, nc.eps, cl.khm, cl.vhm,
                                                   cl.H, cond.kpm)
             else:
-                q = ops.gemm_rows(xp, p["Wq_p"], p["bq"], ln=ln(l.norm_cross))
+                q = ops.gemm_rows(xp, p.Wq.packed, p.bq, ln=ln(l.norm_cross))
                 o = cond.attend(cl, q, packed=True)
-            x, xp = ops.gemm_rows(o, p["Wo_p"], p["bo"], res=x, packed_out="also")
-            f = ops.gemm_rows(xp, p["W1_p"], p["b1"], "gelu", ln=ln(l.norm_ff, cl.gamma_p, cl.beta_p),
+            x, xp = ops.gemm_rows(o, p.Wo.packed, p.bo, res=x, packed_out="also")
+            f = ops.gemm_rows(xp, p.W1.packed, p.b1, "gelu", ln=ln(l.norm_ff, cl.gamma_p, cl.beta_p),
                               packed_out="only")
-            x, xp = ops.gemm_rows(f, p["W2_p"], p["b2"], res=x, packed_out="also")
-        return ops.gemm_rows(xp, c["Wh_p"], c["bh"], ln=ln(m.norm_out))[:, None]
+            x, xp = ops.gemm_rows(f, p.W2.packed, p.b2, res=x, packed_out="also")
+        return ops.gemm_rows(xp, c.Wh.packed, c.bh, ln=ln(m.norm_out))[:, None]
 
     def step_fn(self, logprobs):
         """The step generate() and a session run: the fused step, or the
         generic one -- with log-probabilities asked for, its BLAS projections
         at BLAS_ROWS rows, so that the values do not depend on the row count;
         without, exactly as decode_step runs it."""
-        if self.fused:
+        if self.ctx.fused:
             return self._step_rows
         if not logprobs:
             return self._step
@@ -513,15 +443,15 @@ class DecodeEngine:
     # -- one step, eager -----------------------------------------------------
     def _step(self, tok, pos, states, rows=0):
         m, c = self.m, self.ctx
-        cd, cond = c["cd"], c["cond"]
+        cd, cond = c.cd, c.cond
         x = (F.embedding(tok, m.token_embed.weight) + F.embedding(pos, m.pos_embed.weight)[:, None]).to(cd)
-        x = x.view(c["B"], -1)                                               # (B, d)
+        x = x.view(c.rows, -1)                                               # (B, d)
         proj = _proj_rows if (self.use_rows and cd == torch.bfloat16) else _proj_blas
 
         def mm_(x, w, b=None, act=None):   # rows > 0: the BLAS projections at that fixed row count (_proj_blas)
             return proj(x, w, b, act, rows)
         pending = None
-        for i, (l, p, cl) in enumerate(zip(m.layers, c["layers"], cond.layers)):
+        for i, (l, p, cl) in enumerate(zip(m.layers, c.layers, cond.layers)):
             conv_state, ssm_state = states[i]
             h, xs = ops.layer_norm(x if pending is None else pending, l.norm_mamba.weight, l.norm_mamba.bias,
                                    l.norm_mamba.eps, res=None if pending is None else x)
@@ -529,22 +459,22 @@ class DecodeEngine:
                 x = xs
             mm = l.mamba
             di, N, r = mm.d_inner, mm.d_state, mm.dt_rank
-            xz = mm_(h, p["Win"])
-            u = ops.conv_update(xz[:, :di], conv_state, p["conv_w"], p["conv_b"], True)
-            x_dbl = mm_(u, p["Wx"])
+            xz = mm_(h, p.Win.w)
+            u = ops.conv_update(xz[:, :di], conv_state, p.conv_w, p.conv_b, True)
+            x_dbl = mm_(u, p.Wx.w)
             # dt_proj fused into the state update; B / C read in place from x_dbl
-            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p["A"], x_dbl[:, r:r + N], x_dbl[:, r + N:], p["D"],
-                                 xz[:, di:], p["dt_bias"], True, dt_w=p["Wdt"])
-            h_m = mm_(y, p["Wout"])
+            y = ops.state_update(ssm_state, u, x_dbl[:, :r], p.A, x_dbl[:, r:r + N], x_dbl[:, r + N:], p.D,
+                                 xz[:, di:], p.dt_bias, True, dt_w=p.Wdt)
+            h_m = mm_(y, p.Wout.w)
             h, x = ops.layer_norm(h_m, l.norm_cross.weight, l.norm_cross.bias, l.norm_cross.eps, res=x)
-            q = mm_(h, p["Wq"], p["bq"])
+            q = mm_(h, p.Wq.w, p.bq)
             o = cond.attend(cl, q, packed=False)
-            a = mm_(o, p["Wo"], p["bo"])
+            a = mm_(o, p.Wo.w, p.bo)
             h, x = ops.layer_norm(a, l.norm_ff.weight, l.norm_ff.bias, l.norm_ff.eps, res=x,
                                   gamma=cl.gamma, beta=cl.beta, rows_per_group=1)
-            pending = mm_(mm_(h, p["W1"], p["b1"], "gelu"), p["W2"], p["b2"])
+            pending = mm_(mm_(h, p.W1.w, p.b1, "gelu"), p.W2.w, p.b2)
         h, _ = ops.layer_norm(pending, m.norm_out.weight, m.norm_out.bias, m.norm_out.eps, res=x)
-        return mm_(h, c["Wh"], c["bh"])[:, None]
+        return mm_(h, c.Wh.w, c.bh)[:, None]
 
     # -- out-of-range token ids --------------------------------------------------
     def _check_token_flag(self, dev, blocking=False):
@@ -590,40 +520,13 @@ class DecodeEngine:
         key = (cd, tok_shape) if kv_dtype is None else (cd, tok_shape, kv_dtype)
         B = tok_shape[0]
         if key != self.ctx_key or not _same_ctx(self.ctx_refs, self.ctx_versions, conds):
-            # the split-key routing is latched here, with the context: _xpk_ok and every later step agree on it
-            self.ctx = self._build_ctx(Conditioning.from_batch(m, *conds, cd, kv_dtype, self.OPTIONS["split_keys"]))
+            self.drop()
+            # the split-key routing is latched here, with the conditioning: the context's latch and every step agree
+            cond = Conditioning.from_batch(m, *conds, cd, kv_dtype, self.OPTIONS["split_keys"])
+            self.adopt(DecodeContext.build(m, cond, B, self.use_rows), B, dev)
             self.ctx_key = key
             self.ctx_refs = conds                  # strong references (see _same_ctx)
             self.ctx_versions = tuple(None if t is None else t._version for t in conds)
-            self._latch_routing(B)
-            self.graph = None
-            self.gen_graphs = {}
-            self.gen = None
-            self.states = None
-        if self.states is None:
-            self._alloc_state(B, dev)
-
-    def _latch_routing(self, B):
-        """Which step runs over self.ctx at B rows, decided once per context:
-        the fused-epilogue step, its packed weights, the packed activations
-        (with the head-major K / V and the packed FiLM images they read) and
-        the q projection inside the attention kernel."""
-        self.fused = self._fused_ok(self.ctx["cd"], B)
-        if self.fused and self.OPTIONS["packed"]:
-            self._pack_ctx()
-        self.xpk = self.fused and self._xpk_ok()
-        if self.xpk:
-            self.ctx["cond"].make_packed_images()
-        self.fuse_q = self.xpk and self.OPTIONS["fuse_q"] and self._fuse_q_ok(B)
-
-    def _alloc_state(self, B, dev):
-        """The static per-layer (conv, SSM) states and token / position buffers of B rows, zeroed."""
-        self.states = [(torch.zeros(B, l.mamba.d_inner, l.mamba.d_conv, device=dev),
-                        torch.zeros(B, l.mamba.d_inner, l.mamba.d_state, device=dev)) for l in self.m.layers]
-        self.tok_buf = torch.zeros(B, 1, dtype=torch.long, device=dev)
-        # per-row positions: int64 for the eager step's F.embedding, int32 for the fused step
-        self.pos_buf = torch.zeros(B, dtype=torch.long, device=dev)
-        self.pos32 = torch.zeros(B, dtype=torch.int32, device=dev)
 
     # -- public ----------------------------------------------------------------
     @torch.no_grad()
@@ -644,7 +547,7 @@ class DecodeEngine:
                 st[0].copy_(given[0])
                 st[1].copy_(given[1])
         self.tok_buf.copy_(last_token)
-        pbuf = self.pos32 if self.fused else self.pos_buf   # the fused step embeds int32 position ids
+        pbuf = self.step_pos                                # this one alone: the timed loop gets no second launch
         if isinstance(step_index, torch.Tensor) and step_index.dim() > 0:   # per-row positions
             if tuple(step_index.shape) != (B,) or step_index.dtype.is_floating_point or step_index.dtype == torch.bool:
                 raise ValueError(f"decode_step: a tensor step_index must be ({B},) integers, one position per row")
@@ -655,10 +558,10 @@ class DecodeEngine:
             if not 0 <= int(step_index) < m.pos_embed.num_embeddings:   # pos_embed(step_index) raises (:226)
                 raise IndexError("index out of range in self")
             pbuf.fill_(int(step_index))
-        step = self._step_rows if self.fused else self._step
+        step = self._step_rows if self.ctx.fused else self._step
         if not self.use_graph:
             logits = step(self.tok_buf, self.pos_buf, self.states)
-            if self.fused:
+            if self.ctx.fused:
                 self._post_token_flag(dev)
             return logits, list(self.states)
         if self.graph is None:
@@ -671,7 +574,7 @@ class DecodeEngine:
 
             self.graph, self.out_buf = capture_graph(lambda: step(self.tok_buf, self.pos_buf, self.states), restore)
         self.graph.replay()
-        if self.fused:
+        if self.ctx.fused:
             self._post_token_flag(dev)
         return self.out_buf.clone(), list(self.states)
 
@@ -734,12 +637,12 @@ class DecodeEngine:
         head reads the row's position lens[b] - 1."""
         m, c = self.m, self.ctx
         text_hidden, z_style, text_mask, ref_hidden, ref_mask = conds
-        cd = c["cd"]
+        cd = c.cd
         B, Tp = prompt.shape
         th = text_hidden.to(cd)
         th, tm = m._concat_ref(th, text_mask, ref_hidden, ref_mask, B, th.device)
         qid = torch.zeros(Tp, dtype=torch.long, device=prompt.device)
-        x = embed_sum(prompt, qid, m.token_embed.weight, c["q0_w"], m.pos_embed.weight, cd)
+        x = embed_sum(prompt, qid, m.token_embed.weight, c.q0_w, m.pos_embed.weight, cd)
         with cast_scope(m._gemm_weights(), cd):
             if lens is None:
                 x, pending, new_states = m._run_layers(x, th, z_style, tm, None)
@@ -858,13 +761,13 @@ class DecodeEngine:
         conds = (text_hidden, z_style, text_mask, ref_hidden, ref_mask)
         self._prepare(conds, (B, 1), dev, kv_dtype)
         g = self._gen_buffers(B, V, dev, bool(return_logprobs))
-        stepfn = self.step_fn(bool(return_logprobs))
+        stepfn, fused, pos = self.step_fn(bool(return_logprobs)), self.ctx.fused, self.step_pos
         eos = None if eos_id is None else int(eos_id)
 
         def draw(logits):
             common = dict(logit_bias=g["bias"], step=g["step"], advance=True, out=self.tok_buf, history=g["hist"],
                           eos_id=eos, pad_id=int(pad_id), finished=g["finished"], length=g["length"],
-                          unfinished=g["unfinished"], pos=self.pos32 if self.fused else None)
+                          unfinished=g["unfinished"], pos=pos if fused else None)
             if return_logprobs:
                 common["logprob_history"] = g["lp_hist"]
             if per_row:
@@ -874,8 +777,8 @@ class DecodeEngine:
             else:
                 ops.sample_tokens(logits, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
                                   seed=g["seed"], **common)
-            if not self.fused:
-                self.pos_buf.add_(1)
+            if not fused:                           # the sampler advances the fused step's int32 positions only
+                pos.add_(1)
 
         def body():
             draw(stepfn(self.tok_buf, self.pos_buf, self.states)[:, 0])
@@ -916,12 +819,7 @@ class DecodeEngine:
         if Tp > 1:
             logits0 = self._prefill(prompt_tokens.long(), conds, lens)
             self.prefill_logits = logits0
-            if lens is None:
-                self.pos32.fill_(Tp - 1)
-                self.pos_buf.fill_(Tp - 1)
-            else:                                   # row b continues from its own last prompt position
-                self.pos32.copy_(lens - 1)
-                self.pos_buf.copy_(lens - 1)
+            self.set_pos(Tp - 1 if lens is None else lens - 1)  # row b continues from its own last prompt position
             draw(logits0)                           # token 0 from the prompt's last logits; pos -> Tp
             issued = 1
         elif prompt_tokens is not None:
@@ -942,7 +840,7 @@ class DecodeEngine:
                         break
                 prev = ev
                 polls += 1
-        if self.fused:
+        if self.ctx.fused:
             self._post_token_flag(dev)
         torch.cuda.current_stream().synchronize()
         self.check_errors()

@@ -40,6 +40,7 @@ import torch
 
 from . import ops
 from .conditioning import Conditioning
+from .context import DecodeContext
 from .decode import (DecodeEngine, _check_request, _check_vocab_ids, _check_window, _is_scalar, capture_graph,
                      check_kv_dtype, check_split_keys, sampler_buffers)
 
@@ -119,18 +120,15 @@ class DecodeSession:
         self.dev = dev
         cd = self.cd = m._cd()
         P = self.P = m.pos_embed.num_embeddings
-        # a private engine over a context of `slots` idle rows, routed and given its buffers by its own methods
+        # a private engine over a context of `slots` idle rows, built and routed as generate()'s is
         eng = self.eng = DecodeEngine(m, use_graph=False)
         cond = self.cond = Conditioning.idle(slots, max_keys, cd, dev, kv_dtype, eng.OPTIONS["split_keys"], share_keys)
         self.kpm, self.kv_lens, self.kv_rows = cond.kpm, cond.kv_lens, cond.kv_rows
-        ctx = eng.ctx = eng._build_ctx(cond)
-        eng._latch_routing(slots)
-        eng._alloc_state(slots, dev)
+        eng.adopt(DecodeContext.build(m, cond, slots, eng.use_rows), slots, dev)
         eng.tok_buf.fill_(self.pad)
-        # the batch-1 prefill runs on an engine of its own states; the context's constants are shared
-        pre = self.pre = DecodeEngine(m, use_graph=False)
-        pre.ctx = ctx
-        pre._alloc_state(1, dev)
+        # the batch-1 prefill runs on an engine of its own states; the context, constants and routing, is shared
+        self.pre = DecodeEngine(m, use_graph=False)
+        self.pre.adopt(eng.ctx, 1, dev)
         # length (int64) and finished (int32) share one allocation: a poll is one copy
         self._raw = torch.zeros(12 * slots, dtype=torch.uint8, device=dev)
         self._raw_host = torch.zeros(12 * slots, dtype=torch.uint8, pin_memory=True)
@@ -163,10 +161,10 @@ class DecodeSession:
             max_length=g["max_length"][rows], logit_bias=g["bias"][rows], advance=True, out=eng.tok_buf[rows],
             history=g["hist"][rows], eos_id=self.eos, pad_id=self.pad, finished=self.finished[rows],
             length=self.length[rows], unfinished=g["unfinished"] if rows == slice(None) else None,
-            pos=eng.pos32[rows] if eng.fused else None,
+            pos=eng.step_pos[rows] if eng.ctx.fused else None,
             logprob_history=g["lp_hist"][rows] if self.logprobs else None)
-        if not eng.fused:                                   # the generic step's int64 positions: the same rule
-            eng.pos_buf[rows] += (self.finished[rows] == 0).to(torch.int64)
+        if not eng.ctx.fused:                               # the generic step's int64 positions: the same rule
+            eng.step_pos[rows] += (self.finished[rows] == 0).to(torch.int64)
 
     def _body(self):
         """Step + sampler.  Under a graph the step's own output is the static
@@ -186,8 +184,7 @@ class DecodeSession:
             cs.zero_()
             ss.zero_()
         eng.tok_buf.fill_(self.pad)
-        eng.pos_buf.zero_()
-        eng.pos32.zero_()
+        eng.set_pos(0)
         self.finished.fill_(1)
         self.length.zero_()
         self.g["draw"].zero_()
@@ -334,15 +331,13 @@ class DecodeSession:
                 for (cs, ss), (c1, s1) in zip(eng.states, self.pre.states):
                     cs[r].copy_(c1[0])
                     ss[r].copy_(s1[0])
-                eng.pos32[r:r + 1].fill_(Tp - 1)
-                eng.pos_buf[r:r + 1].fill_(Tp - 1)
+                eng.set_pos(Tp - 1, slice(r, r + 1))
                 self._sample(logits0, slice(r, r + 1))      # token 0 from the prompt's last logits; pos -> Tp
             else:
                 eng.tok_buf[r].fill_(int(start_token) if pt is None else 0)
                 if pt is not None:
                     eng.tok_buf[r].copy_(pt[0])
-                eng.pos32[r:r + 1].zero_()
-                eng.pos_buf[r:r + 1].zero_()
+                eng.set_pos(0, slice(r, r + 1))
             self.state[r] = "live"
 
     def _make_idle(self, r):
@@ -351,15 +346,14 @@ class DecodeSession:
         self.holder[r] = r
         self.finished[r:r + 1].fill_(1)
         eng.tok_buf[r].fill_(self.pad)
-        eng.pos32[r:r + 1].zero_()
-        eng.pos_buf[r:r + 1].zero_()
+        eng.set_pos(0, slice(r, r + 1))
         self.state[r] = "idle"
 
     def poll(self):
         """The slots whose request has finished and has not been taken: one
         copy of finished / length to pinned memory, waited for.  Raises
         IndexError when a step embedded a token id outside token_embed."""
-        if self.eng.fused:
+        if self.eng.ctx.fused:
             self.eng._post_token_flag(self.dev)
         self._raw_host.copy_(self._raw, non_blocking=True)
         torch.cuda.current_stream().synchronize()

@@ -25,10 +25,10 @@ _models = {}
 
 
 def _setup(fmt):
-    """The format's model, and `make`: a context's Conditioning, routed by an engine of its own -- the idle rows, or
-    built from the conditioning batch given."""
+    """The format's model, and `make`: a Conditioning and the context over it, routed unless told otherwise -- the
+    idle rows, or built from the conditioning batch given."""
     from mtts.conditioning import Conditioning
-    from mtts.decode import DecodeEngine
+    from mtts.context import DecodeContext
     cd, kv_dtype, shared = FORMATS[fmt]
     if cd not in _models:
         _models[cd] = _decoder(cd)
@@ -41,12 +41,11 @@ def _setup(fmt):
             else:
                 th, keep, z = batch
                 cond = Conditioning.from_batch(m, th, z, keep, None, None, m._cd(), kv_dtype, True)
-            eng = DecodeEngine(m, use_graph=False)
-            eng.ctx = eng._build_ctx(cond)
+            ctx = DecodeContext(m, cond)
             if latch:
-                eng._latch_routing(cond.rows)
-                assert eng.xpk == (fmt != "fp32")
-        return cond, eng
+                ctx.latch(cond.rows)
+                assert ctx.xpk == (fmt != "fp32")
+        return cond, ctx
 
     return m, make
 
@@ -135,12 +134,13 @@ def test_copy_is_copy(fmt):
 @pytest.mark.parametrize("fmt", ["bf16", "fp8"])
 def test_the_routing_predicate_is_pure(fmt):
     m, make = _setup(fmt)
-    cond, eng = make(latch=False)
-    eng.fused = eng._fused_ok(cond.cd, ROWS)
-    eng._pack_ctx()
-    assert eng.fused and eng._xpk_ok() is True and eng._xpk_ok() is True
+    from mtts.context import fused_ok
+    cond, ctx = make(latch=False)
+    ctx.fused = fused_ok(m, cond.cd, ROWS, True)
+    ctx.pack_weights()
+    assert ctx.fused and ctx.xpk_ok() is True and ctx.xpk_ok() is True
     assert all(t is None for c in cond.layers for t in (c.khm, c.vhm, c.gamma_p, c.beta_p))
-    assert eng._fuse_q_ok(ROWS) is False                    # 520 keys: past the single-pass range; it reads no image
+    assert ctx.fuse_q_ok(ROWS) is False                    # 520 keys: past the single-pass range; it reads no image
     cond.make_packed_images()
     assert all(c.gamma_p is not None and c.beta_p is not None for c in cond.layers)
     assert all((c.khm is not None and c.vhm is not None) == (fmt == "bf16") for c in cond.layers)

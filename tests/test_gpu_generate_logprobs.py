@@ -86,7 +86,7 @@ def test_generate_returns_logprobs_and_moves_no_token(V, cd, mode):
     rows = dict(text_mask=mask, repetition_penalty=PENALTY, repetition_window=WINDOW, **MIXED)
     for kw in (scalar, rows):
         toks, lens = m.generate(text, z, N, **kw)
-        assert m._engine.fused == (cd == torch.bfloat16)
+        assert m._engine.ctx.fused == (cd == torch.bfloat16)
         g0 = graphs()
         out = m.generate(text, z, N, return_logprobs=True, **kw)
         assert len(out) == 3 and graphs() == g0 + per_call                  # a graph of its own

@@ -69,13 +69,13 @@ def test_long_keys_keep_the_packed_step(model, monkeypatch):
     from mtts.decode import DecodeEngine
     assert DecodeEngine.OPTIONS["split_keys"] is True
     ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert ses.eng.fused and ses.eng.xpk and ses.cond.layers[0].khm is not None
-    assert ses.eng.ctx["cond"].kv_lens is ses.kv_lens and ses.kv_lens.dtype == torch.int32
+    assert ses.eng.ctx.fused and ses.eng.ctx.xpk and ses.cond.layers[0].khm is not None
+    assert ses.eng.ctx.cond.kv_lens is ses.kv_lens and ses.kv_lens.dtype == torch.int32
     assert ses.kv_lens.tolist() == [1] * SLOTS              # an idle slot's only key is key 0
-    assert not ses.eng.fuse_q
+    assert not ses.eng.ctx.fuse_q
     monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", False)
     old = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert old.eng.fused and not old.eng.xpk and old.cond.layers[0].khm is None
+    assert old.eng.ctx.fused and not old.eng.ctx.xpk and old.cond.layers[0].khm is None
 
 
 def _conds():
@@ -110,7 +110,7 @@ def test_bf16_step_matches_the_module_path(model, mode):
     try:
         got = _six_steps(model, mode, text, z, mask, tok)
         eng = model._engine
-        assert eng.fused and eng.xpk and eng.ctx["cond"].kv_lens.tolist() == [KEYS, 300, CK + 1]
+        assert eng.ctx.fused and eng.ctx.xpk and eng.ctx.cond.kv_lens.tolist() == [KEYS, 300, CK + 1]
         want = _six_steps(model, None, text, z, mask, tok)
     finally:
         model.decode_mode = "graph"
@@ -128,7 +128,7 @@ def test_fp32_step_matches_the_module_path(mode):
     m = _decoder(None)
     text, z, mask, tok = _conds()
     got = _six_steps(m, mode, text, z, mask, tok)
-    assert not m._engine.fused and m._engine.ctx["cond"].kv_lens.tolist() == [KEYS, 300, CK + 1]
+    assert not m._engine.ctx.fused and m._engine.ctx.cond.kv_lens.tolist() == [KEYS, 300, CK + 1]
     want = _six_steps(m, None, text, z, mask, tok)
     err = (got - want).abs().max().item() / want.abs().max().item()
     print(f"fp32 engine ({mode}) vs module path at {KEYS} keys: {err:.3e} of the logit scale")
@@ -141,7 +141,7 @@ def test_a_request_of_any_key_count_runs_the_same_anywhere(model, keys):
     req = _req(keys, 0)
     others = [k for k in (5, CK, CK + 1, KEYS) if k != keys]
     ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert ses.eng.xpk
+    assert ses.eng.ctx.xpk
     want = _solo(ses, 1, req)                               # slot 1 of an otherwise idle session
     assert want.shape == (CAP,) and len(torch.unique(want)) > 3
     ses.admit(0, **_req(others[0], 1, cap=40))
@@ -185,7 +185,7 @@ def test_short_conditioning_is_untouched(model, monkeypatch):
     for on in (True, False):
         monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", on)
         ses = model.open_session(SLOTS, 16, repetition_window=WINDOW)
-        assert ses.eng.xpk
+        assert ses.eng.ctx.xpk
         ses.admit(3, **req)
         ses.run(CAP)
         logits = ses.logits.clone()
@@ -203,12 +203,12 @@ def test_routing_is_fixed_when_the_context_is_built(model, monkeypatch):
     model.decode_mode = "eager"
     try:
         ses = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-        assert ses.captures == 0 and ses.eng.xpk and ses.cond.split is True
+        assert ses.captures == 0 and ses.eng.ctx.xpk and ses.cond.split is True
         want = _solo(ses, 1, req)
         monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", False)
         assert torch.equal(_solo(ses, 1, req), want)        # still the packed step on the split kernel
         old = model.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-        assert not old.eng.xpk and old.cond.split is False
+        assert not old.eng.ctx.xpk and old.cond.split is False
         monkeypatch.setitem(DecodeEngine.OPTIONS, "split_keys", True)
         assert _solo(old, 1, req).shape == (CAP,)           # still the parent's routing: no packed call is made
         assert old.cond.split_ws is None and ses.cond.split_ws is not None

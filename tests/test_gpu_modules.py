@@ -237,6 +237,7 @@ def test_bf16_decode_engine_c4_shapes(B):
     projections) against the generic module path, bf16, several steps.
     Bound: 3e-2 of the logit scale (bf16 roundings of the activations)."""
     import mamba_decoder
+    from mtts.context import fused_ok
     from mtts.decode import DecodeEngine
     torch.manual_seed(1)
     m = mamba_decoder.MambaTTSDecoder(10, d_model=1024, n_layers=2, n_heads=8, d_ff=2048, d_style=256).to(DEV).eval()
@@ -261,7 +262,7 @@ def test_bf16_decode_engine_c4_shapes(B):
                     lg, states = m.decode_step(tok, text, z, states, t, text_mask=mask)
                 seq.append(lg.float().clone())
         outs.append(torch.cat(seq, 1))
-    assert (B <= 32) == DecodeEngine(m)._fused_ok(torch.bfloat16, B)
+    assert (B <= 32) == fused_ok(m, torch.bfloat16, B, True)
     close(outs[0], outs[1], rtol=3e-2, name=f"engine vs module path, B={B}")
 
 
@@ -286,7 +287,7 @@ def test_decode_engine_out_of_range_token_raises():
     bad[2, 0] = 10
     with torch.no_grad():
         lg, st = m.decode_step(good, text, z, [None, None], 0)
-        assert m._engine.fused
+        assert m._engine.ctx.fused
         lg, st = m.decode_step(bad, text, z, st, 1)
         assert torch.isfinite(lg).all()
         torch.cuda.synchronize()

@@ -47,7 +47,7 @@ def test_slot_sampler_inside_the_session(mode, cd):
     m = _model(cd)
     m.decode_mode = mode
     ses = m.open_session(SLOTS, KEYS, repetition_window=WINDOW)
-    assert ses.eng.fused == (cd == torch.bfloat16)
+    assert ses.eng.ctx.fused == (cd == torch.bfloat16)
     assert ses.captures == (1 if mode == "graph" else 0)
     reqs = [_request(0, 30), _request(1, 36), _request(2, 20)]
     ctl = dict(temperature=[r["temperature"] for r in reqs], top_k=[r["top_k"] for r in reqs],
@@ -63,7 +63,7 @@ def test_slot_sampler_inside_the_session(mode, cd):
             ses.admit(2, **reqs[2])                         # five replays late: the rows sit at different columns
         draw, fin = ses.g["draw"].cpu().tolist(), ses.finished.cpu().tolist()
         hist, length = ses.g["hist"].cpu().numpy(), ses.length.cpu().tolist()
-        pos = (ses.eng.pos32 if ses.eng.fused else ses.eng.pos_buf).cpu().tolist()
+        pos = ses.eng.step_pos.cpu().tolist()
         ses.run(1)
         lg = ses.logits.float().cpu().numpy()
         tok = ses.eng.tok_buf[:, 0].cpu().numpy()
@@ -77,7 +77,7 @@ def test_slot_sampler_inside_the_session(mode, cd):
                 live[r] = False
         assert np.array_equal(ses.g["hist"].cpu().numpy(), after["history"]), t
         assert ses.g["draw"].cpu().tolist() == after["draw"] and ses.finished.cpu().tolist() == after["finished"], t
-        assert (ses.eng.pos32 if ses.eng.fused else ses.eng.pos_buf).cpu().tolist() == after["pos"], t
+        assert ses.eng.step_pos.cpu().tolist() == after["pos"], t
     assert ses.logits is logits0                            # the logits buffer is static
     assert sum(live) >= SLOTS - 1, live
     assert sorted(ses.poll()) == [0, 1, 2]
@@ -129,7 +129,7 @@ def test_packed_step_slots_in_both_halves_of_the_image():
 
     r0, r1, r2 = req(0, 20), req(1, 30), req(2, 30)
     ses = m.open_session(20, KEYS, repetition_window=WINDOW)
-    assert ses.eng.xpk and ses.cond.layers[0].khm is not None and ses.cond.layers[0].gamma_p is not None
+    assert ses.eng.ctx.xpk and ses.cond.layers[0].khm is not None and ses.cond.layers[0].gamma_p is not None
     packed = ses.cond.layers[0].gamma_p.data
     want = _solo(ses, 1, r0)
     assert len(torch.unique(want)) > 3

@@ -79,7 +79,7 @@ def test_a_request_runs_the_same_anywhere_bf16(model, keys, mode):
     model.decode_mode = mode
     try:
         _anywhere(model, keys)
-        assert model._engine.fused and model._engine.xpk    # the packed step
+        assert model._engine.ctx.fused and model._engine.ctx.xpk    # the packed step
     finally:
         model.decode_mode = "graph"
 
@@ -88,7 +88,7 @@ def test_a_request_runs_the_same_anywhere_fp32():
     m = _decoder(None)                                      # fp32: the generic step
     m.decode_mode = "graph"
     _anywhere(m, CK + 1)
-    assert not m._engine.fused
+    assert not m._engine.ctx.fused
 
 
 def test_stale_keys_do_not_leak(model):
@@ -126,7 +126,7 @@ def test_admit_samples_members_are_admits_with_their_seeds(model):
 def test_the_session_holds_fp8_keys_and_no_bf16_image(model):
     model.decode_mode = "graph"
     ses = _open(model)
-    assert ses.captures == 1 and ses.eng.fused and ses.eng.xpk and not ses.eng.fuse_q
+    assert ses.captures == 1 and ses.eng.ctx.fused and ses.eng.ctx.xpk and not ses.eng.ctx.fuse_q
     for p in ses.cond.layers:
         for t in (p.k8, p.v8):
             assert t.shape == (SLOTS, HEADS, KEYS, HD) and t.dtype == torch.uint8
@@ -150,13 +150,13 @@ def test_generate_keeps_fp8_keys_and_rebuilds_on_a_change(model):
     a, _ = model.generate(text, z, 4, kv_dtype="fp8")
     eng = model._engine
     ctx = eng.ctx
-    assert all(p.k8 is not None and all(t is None for t in (p.k, p.v, p.khm, p.vhm)) for p in ctx["cond"].layers)
-    assert ctx["cond"].layers[0].k8.shape == (2, HEADS, KEYS, HD) and eng.ctx_key[-1] == "fp8"
-    assert eng.fused and eng.xpk and not eng.fuse_q
+    assert all(p.k8 is not None and all(t is None for t in (p.k, p.v, p.khm, p.vhm)) for p in ctx.cond.layers)
+    assert ctx.cond.layers[0].k8.shape == (2, HEADS, KEYS, HD) and eng.ctx_key[-1] == "fp8"
+    assert ctx.fused and ctx.xpk and not ctx.fuse_q
     again, _ = model.generate(text, z, 4, kv_dtype="fp8")
     assert eng.ctx is ctx and torch.equal(again, a)         # the same tensors and value: the context is kept
     b, _ = model.generate(text, z, 4)                       # the same tensors, kv_dtype off: a new context
-    assert eng.ctx is not ctx and eng.ctx["cond"].layers[0].k is not None and eng.ctx["cond"].layers[0].k8 is None
+    assert eng.ctx is not ctx and eng.ctx.cond.layers[0].k is not None and eng.ctx.cond.layers[0].k8 is None
     assert len(eng.ctx_key) == 2 and a.shape == b.shape
 
 

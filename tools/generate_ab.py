@@ -79,6 +79,12 @@ def torch_draw(logits, temperature, top_k, top_p):
     return idx.gather(1, torch.multinomial(p, 1))
 
 
+def xpk(ses):
+    """The session steps on packed activations (a package timed through AB_PKG may keep the flag on the engine)."""
+    eng = ses.eng
+    return eng.ctx.xpk if hasattr(eng.ctx, "xpk") else eng.xpk
+
+
 def timed(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -292,7 +298,7 @@ def long_keys_leg(n, dev, lines):
                     ses[leg] = m.open_session(slots, max_keys, repetition_window=64)
                 finally:
                     DecodeEngine.OPTIONS["split_keys"] = True
-            assert ses["s"].eng.xpk and ses["r"].eng.xpk and not ses["p"].eng.xpk
+            assert xpk(ses["s"]) and xpk(ses["r"]) and not xpk(ses["p"])
 
             def run(leg):
                 s = ses[leg]
@@ -354,7 +360,7 @@ def kv_fp8_leg(n, dev, lines):
             counts = torch.randint(600, max_keys + 1, (slots,), generator=g).tolist()
             ses = {"b": m.open_session(slots, max_keys, repetition_window=64),
                    "f": m.open_session(slots, max_keys, repetition_window=64, kv_dtype="fp8")}
-            assert ses["b"].eng.xpk and ses["f"].eng.xpk
+            assert xpk(ses["b"]) and xpk(ses["f"])
             held = {leg: s.cond.kv_bytes() for leg, s in ses.items()}
             kw = dict(temperature=1.0, top_k=50, top_p=0.9)
 
