@@ -17,8 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import attn_kernels
-from . import wgrad as WG
-from .linear import _want_t, cast_scope, cast_weight, cast_weight_t, colsum, linear, proj, wgrad
+from .linear import _want_t, cast_scope, cast_weight, cast_weight_t, linear, param_grads, proj
 
 
 class InProjFn(torch.autograd.Function):
@@ -37,14 +36,14 @@ class InProjFn(torch.autograd.Function):
         q = proj(x2, Wc[:d], bc[:d])
         kv = proj(k2, Wc[d:], bc[d:])
         ctx.save_for_backward(x2, k2, Wc)
-        ctx.weight = weight
-        ctx.meta = (query.shape, key.shape, weight.dtype, bias.dtype)
+        ctx.weight, ctx.bias = weight, bias
+        ctx.meta = (query.shape, key.shape)
         return q.view(*query.shape[:-1], d), kv.view(*key.shape[:-1], 2 * d)
 
     @staticmethod
     def backward(ctx, dq, dkv):
         x2, k2, Wc = ctx.saved_tensors
-        qshape, kshape, wdt, bdt = ctx.meta
+        qshape, kshape = ctx.meta
         d = x2.shape[1]
         dq2 = dq.reshape(-1, d).to(Wc.dtype)
         dkv2 = dkv.reshape(-1, 2 * d).to(Wc.dtype)
@@ -55,18 +54,8 @@ class InProjFn(torch.autograd.Function):
         else:
             dquery = (dq2 @ Wc[:d]).view(qshape) if ctx.needs_input_grad[0] else None
             dkey = (dkv2 @ Wc[d:]).view(kshape) if ctx.needs_input_grad[1] else None
-        dW = db = None
-        if ctx.needs_input_grad[2] and not WG.submit([(dq2, x2, ctx.weight, (0, d)),
-                                                      (dkv2, k2, ctx.weight, (d, 3 * d))]):
-            dW = torch.empty(3 * d, d, device=x2.device, dtype=torch.float32)
-            wgrad(dq2, x2, out=dW[:d])
-            wgrad(dkv2, k2, out=dW[d:])
-            dW = dW.to(wdt)
-        if ctx.needs_input_grad[3]:
-            db = torch.empty(3 * d, device=x2.device, dtype=torch.float32)
-            colsum(dq2, out=db[:d])
-            colsum(dkv2, out=db[d:])
-            db = db.to(bdt)
+        dW, db = param_grads(ctx.weight, ctx.bias, [(dq2, x2, (0, d)), (dkv2, k2, (d, 3 * d))],
+                             ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         return dquery, dkey, dW, db
 
 
@@ -90,21 +79,22 @@ class DkvSink:
         self.written[layer] = True
         return self.buf[:, layer * self.width:(layer + 1) * self.width].view(*self.shape, self.width)
 
-    def partner(self, layer):
-        """For the layer's q projection (linear(..., partner=)): hands over the
-        layer's K/V gradient rows d:3d of in_proj once its attention backward
-        has written them."""
-        sink = self
 
-        class _P:
-            @staticmethod
-            def take():
-                if not sink.written[layer] or sink.buf is None or sink.key2 is None:
-                    return None
-                sink.taken[layer] = True
-                d = sink.width // 2
-                return (sink.buf[:, layer * sink.width:(layer + 1) * sink.width], sink.key2, (d, 3 * d))
-        return _P()
+class DkvPartner:
+    """For a layer's q projection (linear(..., partner=)): take() hands over
+    the layer's K/V part of in_proj -- (dy, x, rows d:3d), linear.param_grads
+    -- once its attention backward has written it into the sink."""
+
+    def __init__(self, sink, layer):
+        self.sink, self.layer = sink, layer
+
+    def take(self):
+        sink, l = self.sink, self.layer
+        if not sink.written[l] or sink.buf is None or sink.key2 is None:
+            return None
+        sink.taken[l] = True
+        d = sink.width // 2
+        return (sink.buf[:, l * sink.width:(l + 1) * sink.width], sink.key2, (d, 3 * d))
 
 
 class KVAllFn(torch.autograd.Function):
@@ -143,12 +133,15 @@ class KVAllFn(torch.autograd.Function):
         nl, d = len(Ws), k2.shape[1]
         w2 = 2 * d
         cd = k2.dtype
-        in_sink = sink.buf is not None and all(
-            g is not None and g.data_ptr() == sink.buf.data_ptr() + l * w2 * sink.buf.element_size()
-            and g.stride()[-2] == nl * w2 for l, g in enumerate(dkvs))
-        if in_sink:
+        own = [sink.buf is not None and g is not None and g.stride()[-2] == nl * w2
+               and g.data_ptr() == sink.buf.data_ptr() + l * w2 * sink.buf.element_size() for l, g in enumerate(dkvs)]
+        for l in range(nl):
+            if sink.taken[l] and not own[l]:
+                raise RuntimeError(f"KVAllFn: layer {l}'s K/V projection has a consumer besides its attention: its "
+                                   "in_proj gradient rows were already produced from the attention's dK / dV alone")
+        if all(own):
             dkv = sink.buf
-        else:   # a layer's gradient arrived elsewhere (unused layer, accumulated use): assemble
+        else:   # a layer's gradient arrived elsewhere (an unused layer): assemble
             dkv = torch.zeros(k2.shape[0], nl * w2, device=k2.device, dtype=cd)
             for l, g in enumerate(dkvs):
                 if g is not None:
@@ -166,17 +159,9 @@ class KVAllFn(torch.autograd.Function):
         # projection (LinearFn partner); only a layer whose q projection did
         # not take them is handled here
         for l in range(nl):
-            W, b = Ws[l], bs[l]
-            dW = db = None
-            if not sink.taken[l]:
-                dy = dkv[:, l * w2:(l + 1) * w2]
-                if ctx.needs_input_grad[2 + 2 * l] and not WG.submit([(dy, k2, W, (d, 3 * d))]):
-                    dW = torch.zeros(W.shape, device=W.device, dtype=W.dtype)
-                    dW[d:] = wgrad(dy.contiguous(), k2).to(W.dtype)
-                if ctx.needs_input_grad[3 + 2 * l]:
-                    db = torch.zeros(b.shape, device=b.device, dtype=b.dtype)
-                    db[d:] = colsum(dy).to(b.dtype)
-            grads += [dW, db]
+            grads += (None, None) if sink.taken[l] else param_grads(
+                Ws[l], bs[l], [(dkv[:, l * w2:(l + 1) * w2], k2, (d, 3 * d))],
+                ctx.needs_input_grad[2 + 2 * l], ctx.needs_input_grad[3 + 2 * l])
         # ready for another backward through the same graph (retain_graph)
         sink.written = [False] * nl
         sink.taken = [False] * nl
@@ -260,7 +245,7 @@ class CrossAttention(nn.Module):
         p_drop = self.dropout if self.training else 0.0
         if kv_pre is not None:
             sk = getattr(kv_pre, "_mtts_dkv_sink", None)
-            q = linear(query, W, b, rows=(0, d), partner=None if sk is None else sk[0].partner(sk[1]))
+            q = linear(query, W, b, rows=(0, d), partner=None if sk is None else DkvPartner(*sk))
             o = attn_kernels.attention_kv(q, kv_pre, H, key_padding_mask, p_drop)
             return linear(o, self.out_proj.weight, self.out_proj.bias, dbias_slot=dbias_slot), None
         if key.shape[1] == 1 and key_padding_mask is None:

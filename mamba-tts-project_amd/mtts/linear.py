@@ -246,6 +246,66 @@ class BiasGradSlot:
         return v if (v is not None and v.numel() == n) else None
 
 
+def _covers_all(n, rows):
+    """True when the row intervals `rows` tile all of [0, n); ValueError when
+    two of them overlap or one leaves [0, n)."""
+    at, whole = 0, True
+    for r0, r1 in sorted(rows):
+        if not at <= r0 < r1 <= n:
+            raise ValueError(f"param_grads: row slices {sorted(rows)} overlap or leave [0, {n})")
+        whole = whole and r0 == at
+        at = r1
+    return whole and at == n
+
+
+def param_grads(weight, bias, parts, need_w, need_b, slot=None):
+    """(dW | None, db | None) of one parameter from its row-slice parts
+    [(dy (M_i, n_i), x (M_i, k), rows (r0, r1) | None = the whole parameter),
+    ...]: dW[rows] = dy^T x, db[rows] = column sums of dy, in the parameter's
+    dtypes, rows that no part covers exactly zero.  The one owner of these
+    decisions for every projection backward (LinearFn alone or with the K/V
+    rows its `partner` hands over, FFNFn, attention.InProjFn / KVAllFn):
+    the weight gradient goes to the grouped engine as ONE job set when it
+    queues (mtts.wgrad; dW is then None), else runs now, part by part into one
+    fp32 buffer; a `slot` delivers the bias gradient of a single part.
+    (mamba.py's two narrow submits stay apart: whole 2-D weights, no bias, no slices, a skinny-TN fallback.)"""
+    n = weight.shape[0]
+    dy0, x0, rows0 = parts[0]
+    whole = len(parts) == 1 and rows0 is None
+    spans = [rows or (0, n) for _, _, rows in parts]
+    if any(dy.shape[1] != r1 - r0 for (dy, _, _), (r0, r1) in zip(parts, spans)):
+        raise ValueError("param_grads: a part's dy width is not its row count")
+    new = torch.empty if _covers_all(n, spans) else torch.zeros
+    dW = db = None
+    if need_w and not WG.submit([(dy, x, weight, rows) for dy, x, rows in parts]):
+        if whole:
+            dW = wgrad(_packed(dy0), x0)
+        else:
+            dW = new(weight.shape, device=weight.device, dtype=torch.float32)
+            for (dy, x, _), (r0, r1) in zip(parts, spans):
+                wgrad(_packed(dy), x, out=dW[r0:r1])
+        dW = dW.to(weight.dtype)
+    if need_b:
+        db = slot.take(dy0.shape[1]) if slot is not None and len(parts) == 1 else None
+        if db is None and whole:
+            db = colsum(dy0)
+        elif not whole:
+            given, db = db, new(n, device=weight.device, dtype=torch.float32)
+            for (dy, _, _), (r0, r1) in zip(parts, spans):
+                if given is not None:
+                    db[r0:r1] = given
+                else:
+                    colsum(dy, out=db[r0:r1])
+        db = db.to(bias.dtype)
+    return dW, db
+
+
+def _packed(dy):
+    """A column slice of a wider buffer (the K/V sink's) is packed for the
+    immediate product; the grouped engine and colsum read it in place."""
+    return dy.contiguous() if dy.stride(1) == 1 and dy.stride(0) > dy.shape[1] else dy
+
+
 class LinearFn(torch.autograd.Function):
     """y = x @ weight[r0:r1]^T + bias[r0:r1] in dtype of x.  Gradients for the
     full weight/bias (zero outside [r0, r1) when a row slice is used)."""
@@ -266,14 +326,14 @@ class LinearFn(torch.autograd.Function):
                 b = b[r0:r1]
         y = proj(x2, w, b)
         ctx.save_for_backward(x2, w)
-        ctx.weight = weight
-        ctx.meta = (x.shape, weight.shape, weight.dtype, None if bias is None else bias.dtype, r0, r1)
+        ctx.weight, ctx.bias = weight, bias
+        ctx.meta = (x.shape, r0, r1)
         return y.view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
-        xshape, wshape, wdt, bdt, r0, r1 = ctx.meta
+        xshape, r0, r1 = ctx.meta
         dy2 = dy.reshape(-1, dy.shape[-1])
         if dy2.dtype != w.dtype:
             dy2 = dy2.to(w.dtype)
@@ -286,50 +346,12 @@ class LinearFn(torch.autograd.Function):
                 dx = proj(dy2, wt).view(xshape)
             else:
                 dx = (dy2 @ w).view(xshape)
-        dW = db = None
-        rest = ctx.partner.take() if ctx.partner is not None else None
-        if rest is not None and r0 is not None:
-            # this projection also owns the parameter's other rows (rest: the
-            # layer's K/V rows of in_proj, attention.KVAllFn): ONE submit and
-            # ONE bias tensor for the whole parameter -- no zero fills, copies
-            # or autograd adds, and the weight gradient stays in this layer's
-            # grouped launch
-            dyr, xr, (q0, q1) = rest
-            if ctx.needs_input_grad[1] and not WG.submit([(dy2, x2, ctx.weight, (r0, r1)),
-                                                          (dyr, xr, ctx.weight, (q0, q1))]):
-                dW = torch.empty(wshape, device=dy2.device, dtype=torch.float32)
-                wgrad(dy2, x2, out=dW[r0:r1])
-                wgrad(dyr.contiguous(), xr, out=dW[q0:q1])
-                if r1 - r0 + q1 - q0 < wshape[0]:
-                    for a, b in ((0, min(r0, q0)), (max(r1, q1), wshape[0])):
-                        if b > a:
-                            dW[a:b].zero_()
-                dW = dW.to(wdt)
-            if bdt is not None and ctx.needs_input_grad[2]:
-                db = torch.empty(wshape[0], device=dy2.device, dtype=torch.float32)
-                colsum(dy2, out=db[r0:r1])
-                colsum(dyr, out=db[q0:q1])
-                if r1 - r0 + q1 - q0 < wshape[0]:
-                    for a, b in ((0, min(r0, q0)), (max(r1, q1), wshape[0])):
-                        if b > a:
-                            db[a:b].zero_()
-                db = db.to(bdt)
-            return dx, dW, db, None, None, None, None
-        if ctx.needs_input_grad[1] and not WG.submit([(dy2, x2, ctx.weight, None if r0 is None else (r0, r1))]):
-            g = wgrad(dy2, x2).to(wdt)
-            if r0 is not None:
-                full = torch.zeros(wshape, device=g.device, dtype=wdt)
-                full[r0:r1] = g
-                g = full
-            dW = g
-        if bdt is not None and ctx.needs_input_grad[2]:
-            gb = ctx.slot.take(dy2.shape[1]) if ctx.slot is not None else None
-            gb = (gb if gb is not None else colsum(dy2)).to(bdt)
-            if r0 is not None:
-                full = torch.zeros(wshape[0], device=gb.device, dtype=bdt)
-                full[r0:r1] = gb
-                gb = full
-            db = gb
+        # a partner's part (attention.DkvPartner: the layer's K/V rows of in_proj)
+        # joins this one: one job set and one bias tensor for the whole parameter
+        rows = None if r0 is None else (r0, r1)
+        rest = ctx.partner.take() if ctx.partner is not None and rows is not None else None
+        dW, db = param_grads(ctx.weight, ctx.bias, [(dy2, x2, rows)] + ([rest] if rest is not None else []),
+                             ctx.needs_input_grad[1], ctx.bias is not None and ctx.needs_input_grad[2], ctx.slot)
         return dx, dW, db, None, None, None, None
 
 
@@ -371,15 +393,14 @@ class FFNFn(torch.autograd.Function):
             a = DO.apply_mask(a, p, ctx.seed, seed_in=base, seed_out=ctx.used)
         y = proj(a, W2, B2)
         ctx.save_for_backward(h2, pre, a, W1, W2)
-        ctx.ws = (w1, w2)
-        ctx.meta = (h.shape, w1.dtype, b1.dtype, w2.dtype, b2.dtype)
+        ctx.params = (w1, b1, w2, b2)
+        ctx.hshape = h.shape
         return y.view(*h.shape[:-1], W2.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         h2, pre, a, W1, W2 = ctx.saved_tensors
-        hshape, w1dt, b1dt, w2dt, b2dt = ctx.meta
-        w1, w2 = ctx.ws
+        w1, b1, w2, b2 = ctx.params
         dy2 = dy.reshape(-1, dy.shape[-1]).to(W2.dtype)
         # d(pre) = (dy W2) * gelu'(pre), one GEMM (W2^T copy: k-contiguous operand);
         # with dropout: the dropout kernel applies the mask and gelu'(pre)
@@ -395,17 +416,9 @@ class FFNFn(torch.autograd.Function):
                 dh = proj(dpre, cast_weight_t(w1, W1.dtype))
             else:
                 dh = dpre @ W1
-            dh = dh.view(hshape)
-        dW1 = dW2 = None   # both straight to the grouped engine when deferral is on (mtts.wgrad)
-        if ctx.needs_input_grad[1] and not WG.submit([(dpre, h2, w1, None)]):
-            dW1 = wgrad(dpre, h2).to(w1dt)
-        db1 = colsum(dpre).to(b1dt) if ctx.needs_input_grad[2] else None
-        if ctx.needs_input_grad[3] and not WG.submit([(dy2, a, w2, None)]):
-            dW2 = wgrad(dy2, a).to(w2dt)
-        db2 = None
-        if ctx.needs_input_grad[4]:
-            db2 = ctx.slot.take(dy2.shape[1]) if ctx.slot is not None else None
-            db2 = (db2 if db2 is not None else colsum(dy2)).to(b2dt)
+            dh = dh.view(ctx.hshape)
+        dW1, db1 = param_grads(w1, b1, [(dpre, h2, None)], ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        dW2, db2 = param_grads(w2, b2, [(dy2, a, None)], ctx.needs_input_grad[3], ctx.needs_input_grad[4], ctx.slot)
         return dh, dW1, db1, dW2, db2, None, None
 
 
