@@ -43,7 +43,9 @@ extern "C" {
  * untouched, and a binding that needs it checks that the symbol resolves.
  * So is its slot form, mtts_sample_tokens_slots: one more symbol on the same
  * struct.  So are the token log-probabilities: three symbols that take the
- * samplers' structs, byte for byte, and one new struct, MttsSampleLogprobOut. */
+ * samplers' structs, byte for byte, and one new struct, MttsSampleLogprobOut.
+ * So is the grouped optimizer step, mtts_clip_adamw, with its four structs:
+ * MttsAdamTensor and mtts_clip_adam are untouched. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -579,6 +581,100 @@ int64_t mtts_adam_workspace(int64_t total_chunks);
 int mtts_clip_adam(const MttsAdamTensor* tensors, int ntensors, int64_t total_chunks, int* step_counter, float lr,
                    float beta1, float beta2, float eps, float weight_decay, float max_norm, void* workspace,
                    float* norm_out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Fused clip + AdamW over parameter groups (an addition to ABI 15; the entry
+ * above is untouched).  The same three launches for the whole list (per-chunk
+ * sums of g^2, one block for the step's scalars, the element pass; no atomics,
+ * fixed summation order), with:
+ *  - up to MTTS_ADAMW_MAX_GROUPS groups in a DEVICE table `groups` (lr,
+ *    weight_decay, decoupled, clip); betas and eps are per call.  Decoupled
+ *    groups follow torch.optim.AdamW (p *= 1 - lr_t * wd, then Adam on
+ *    g * coef), the others torch.optim.Adam's L2 form, as the entry above.
+ *  - the clip norm over the tensors of clipped groups only: the caller puts
+ *    them first, so that they own the chunks [0, clip_chunks).  Tensors of
+ *    unclipped groups use coef = 1.  max_norm <= 0: coef = 1 everywhere, the
+ *    norm is still reported.
+ *  - a learning-rate schedule evaluated on the device, in double, at the
+ *    1-based step t being taken: lr_t = lr_g * f(t).  t <= warmup_steps = W:
+ *    f = t / W.  After it, with x = min(1, (t - W) / (total_steps - W)) and
+ *    r = min_ratio: CONSTANT f = 1; COSINE f = r + (1 - r) (1 + cos(pi x)) / 2;
+ *    LINEAR f = r + (1 - r)(1 - x); INV_SQRT f = max(r, sqrt(max(W, 1) / t)).
+ *    COSINE and LINEAR need total_steps > W.
+ *  - group_steps (device int32 per group) holds each group's steps taken; the
+ *    call increments those whose bit is set in active_groups (the groups with
+ *    a tensor in the list) and derives their bias corrections from them.
+ *    t = 1 + the largest count over all ngroups groups.
+ *  - an exponential moving average: where a tensor's `ema` is not NULL the
+ *    pass also writes e += (1 - d_t)(p_new - e), d_t = ema_decay, or with
+ *    ema_warmup min(ema_decay, (1 + t) / (10 + t)).
+ *  - skip_nonfinite: when the fp32 sum of g^2 over ALL tensors is not finite
+ *    (a NaN or inf gradient element, or an overflow of the fp32 sum itself
+ *    over finite gradients) no counter advances, *skipped is incremented and
+ *    the element pass returns before it loads a tensor element: p, the
+ *    moments and ema stay bit-identical.  With the flag off a NaN norm gives
+ *    a NaN coefficient, as the entry above.
+ * `out` (device, MTTS_ADAMW_OUT_FLOATS floats) receives the step's scalars:
+ * [0] norm over the clipped tensors, [1] coef, [2] f(t), [3] 1 - d_t,
+ * [4] 1.0 when the step was skipped, and per group g: [LR + g] lr_t,
+ * [STEP + g] lr_t / (1 - b1^tg), [BC2 + g] sqrt(1 - b2^tg), [DECAY + g]
+ * 1 - lr_t * wd (1 for an L2 group); tg is the group's own step.  workspace:
+ * mtts_adam_workspace bytes for total_chunks.  Deterministic.
+ * ------------------------------------------------------------------------ */
+#define MTTS_ADAMW_MAX_GROUPS 64
+enum { MTTS_LR_CONSTANT = 0, MTTS_LR_COSINE = 1, MTTS_LR_LINEAR = 2, MTTS_LR_INV_SQRT = 3 };
+enum {
+  MTTS_ADAMW_OUT_LR = 8,
+  MTTS_ADAMW_OUT_STEP = 8 + MTTS_ADAMW_MAX_GROUPS,
+  MTTS_ADAMW_OUT_BC2 = 8 + 2 * MTTS_ADAMW_MAX_GROUPS,
+  MTTS_ADAMW_OUT_DECAY = 8 + 3 * MTTS_ADAMW_MAX_GROUPS,
+  MTTS_ADAMW_OUT_FLOATS = 8 + 4 * MTTS_ADAMW_MAX_GROUPS
+};
+
+typedef struct {
+  float* p;
+  const float* g;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* ema; /* NULL: none */
+  int64_t n;
+  int64_t chunk0;
+  int32_t group;
+  int32_t reserved_;
+} MttsAdamWTensor;
+
+typedef struct {
+  float lr;
+  float weight_decay;
+  int32_t decoupled;
+  int32_t clip;
+} MttsAdamWGroup;
+
+typedef struct {
+  int32_t kind; /* MTTS_LR_* */
+  int32_t warmup_steps;
+  int32_t total_steps;
+  int32_t reserved_;
+  double min_ratio;
+} MttsLrSchedule;
+
+typedef struct {
+  float beta1, beta2, eps;
+  float max_norm;
+  int32_t ngroups;
+  int32_t ema_warmup;
+  int32_t skip_nonfinite;
+  int32_t reserved_;
+  double ema_decay;
+  uint64_t active_groups;
+  int64_t total_chunks;
+  int64_t clip_chunks;
+  MttsLrSchedule schedule;
+} MttsAdamWArgs;
+
+int mtts_clip_adamw(const MttsAdamWTensor* tensors, int ntensors, const MttsAdamWGroup* groups,
+                    const MttsAdamWArgs* args, int* group_steps, int* skipped, void* workspace, float* out,
+                    void* stream);
 
 /* ------------------------------------------------------------------------
  * Embedding sum of the decoder prologue (mamba_decoder.py:167-171:

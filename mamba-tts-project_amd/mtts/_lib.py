@@ -193,6 +193,32 @@ class AdamTensor(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("chunk0", i64)]
 
 
+ADAMW_MAX_GROUPS = 64
+# offsets into mtts_clip_adamw's `out` (include/mtts.h MTTS_ADAMW_OUT_*)
+ADAMW_OUT_LR, ADAMW_OUT_STEP, ADAMW_OUT_BC2, ADAMW_OUT_DECAY, ADAMW_OUT_FLOATS = 8, 72, 136, 200, 264
+LR_KINDS = {"constant": 0, "cosine": 1, "linear": 2, "inverse_sqrt": 3}
+
+
+class AdamWTensor(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("ema", vp), ("n", i64), ("chunk0", i64),
+                ("group", i32), ("reserved_", i32)]
+
+
+class AdamWGroup(C.Structure):
+    _fields_ = [("lr", f32), ("weight_decay", f32), ("decoupled", i32), ("clip", i32)]
+
+
+class LrSchedule(C.Structure):
+    _fields_ = [("kind", i32), ("warmup_steps", i32), ("total_steps", i32), ("reserved_", i32),
+                ("min_ratio", C.c_double)]
+
+
+class AdamWArgs(C.Structure):
+    _fields_ = [("beta1", f32), ("beta2", f32), ("eps", f32), ("max_norm", f32), ("ngroups", i32),
+                ("ema_warmup", i32), ("skip_nonfinite", i32), ("reserved_", i32), ("ema_decay", C.c_double),
+                ("active_groups", C.c_uint64), ("total_chunks", i64), ("clip_chunks", i64), ("schedule", LrSchedule)]
+
+
 _SIGS = {
     "mtts_abi_version": ([], i32),
     "mtts_last_error": ([], C.c_char_p),
@@ -240,6 +266,7 @@ _SIGS = {
     "mtts_adam_chunks": ([i64], i64),
     "mtts_adam_workspace": ([i64], i64),
     "mtts_clip_adam": ([vp, i32, i64, vp, f32, f32, f32, f32, f32, f32, vp, vp, vp], i32),
+    "mtts_clip_adamw": ([vp, i32, vp, C.POINTER(AdamWArgs), vp, vp, vp, vp, vp], i32),
     "mtts_embed_sum": ([vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i64, vp, vp], i32),
     "mtts_embed_sum_at": ([vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i64, vp, i64, i32, vp], i32),
     "mtts_embed_table_grad_workspace": ([i64, i32, i32], i64),
@@ -278,7 +305,8 @@ def lib():
                           ("mtts_attention_decode_split", "long-conditioning decode"),
                           ("mtts_sample_tokens_slots_lp", "token log-probabilities"),
                           ("mtts_attention_decode_split_shared", "shared-key samples"),
-                          ("mtts_attention_decode_split_fp8", "FP8 conditioning K/V")):
+                          ("mtts_attention_decode_split_fp8", "FP8 conditioning K/V"),
+                          ("mtts_clip_adamw", "grouped AdamW step")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "

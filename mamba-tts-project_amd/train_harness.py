@@ -23,9 +23,10 @@ order and with its semantics:
 Adam over all five modules with clipping over the DECODER's parameters only
 (train.py:152-159, 234) = FusedClipAdam(decoder, max_grad_norm=1.0) beside
 FusedClipAdam(others, no clip): Adam is element-wise, so two optimizers with
-the same hyper-parameters are the same update.  With a GradAllReduce (N > 1
-ranks, batch data parallel) the gradients of every trainable parameter are
-all-reduced before the optimizer.
+the same hyper-parameters are the same update (TrainStep(one_optimizer=True):
+one FusedClipAdamW with a clipped and an unclipped group, bit-identical).
+With a GradAllReduce (N > 1 ranks, batch data parallel) the gradients of
+every trainable parameter are all-reduced before the optimizer.
 
 The module shapes follow build_models (train.py:45-70): d_model 512,
 d_style 256, the 80-entry phoneme vocabulary, an 8-layer decoder with 5
@@ -43,7 +44,7 @@ import mamba_decoder
 import style_cross_attention as sca
 import text_encoder as te
 from mtts import wgrad
-from mtts.optim import FusedClipAdam
+from mtts.optim import FusedClipAdam, FusedClipAdamW
 
 C5Models = namedtuple("C5Models", "text_encoder dur_predictor style_pipe decoder")
 
@@ -114,7 +115,10 @@ class TrainStep:
     length read, which the reference makes too)."""
 
     def __init__(self, models: C5Models, lr=1e-4, w_codec=1.0, w_dur=0.1, w_smsd=0.5, grad_allreduce=None,
-                 train_mode=True):
+                 train_mode=True, one_optimizer=False):
+        """one_optimizer: the same update from one FusedClipAdamW with two
+        groups (decoder clipped, the rest not; both L2 with weight_decay 0):
+        three launches and one descriptor plan instead of six and two."""
         self.m = models
         self.w = (w_codec, w_dur, w_smsd)
         for mod in models:
@@ -122,8 +126,13 @@ class TrainStep:
         dec_params = list(models.decoder.parameters())
         rest = [p for mod in (models.text_encoder, models.dur_predictor, models.style_pipe)
                 for p in mod.parameters() if p.requires_grad]
-        self.opt_dec = FusedClipAdam(dec_params, lr=lr, max_grad_norm=1.0)   # clip_grad_norm_(decoder, 1.0)
-        self.opt_rest = FusedClipAdam(rest, lr=lr)
+        self.opt = None
+        if one_optimizer:
+            self.opt = FusedClipAdamW([{"params": dec_params, "clip": True}, {"params": rest, "clip": False}], lr=lr,
+                                      weight_decay=0.0, decoupled=False, max_grad_norm=1.0)
+        else:
+            self.opt_dec = FusedClipAdam(dec_params, lr=lr, max_grad_norm=1.0)   # clip_grad_norm_(decoder, 1.0)
+            self.opt_rest = FusedClipAdam(rest, lr=lr)
         self.dp = grad_allreduce
         self.params = dec_params + rest
 
@@ -166,6 +175,9 @@ class TrainStep:
             self.dp.finish()
 
     def optimizer_step(self):
+        if self.opt is not None:
+            self.opt.step()
+            return
         self.opt_dec.step()                                                        # :234-235
         self.opt_rest.step()
 

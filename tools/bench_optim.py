@@ -1,13 +1,27 @@
 """Optimizer step at the C2 parameter count: FusedClipAdam (mtts_clip_adam)
-vs torch fused Adam + foreach-norm clip (clip_into_optimizer)."""
+vs torch fused Adam + foreach-norm clip (clip_into_optimizer).
+
+--adamw: FusedClipAdam (the parent entry) beside FusedClipAdamW (mtts_clip_adamw)
+with every option off, with the three-group AdamW setup (matrices decoupled wd
+0.01 / vectors wd 0, both clipped; embeddings unclipped L2 at their own lr;
+cosine schedule), and the same with EMA, interleaved round by round in one
+process; prints each configuration's median over the rounds with its spread
+(min .. max)."""
+import argparse
 import os
+import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mamba-tts-project_amd")]
 import torch  # noqa: E402
 import mamba_decoder  # noqa: E402
-from mtts.optim import FusedClipAdam, clip_into_optimizer  # noqa: E402
+from mtts.optim import FusedClipAdam, FusedClipAdamW, LRSchedule, clip_into_optimizer  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--adamw", action="store_true")
+ap.add_argument("--rounds", type=int, default=9)
+args = ap.parse_args()
 
 m = mamba_decoder.MambaTTSDecoder(10, d_model=1024, n_layers=12, n_heads=8, d_ff=2048, d_style=256).cuda()
 ps = list(m.parameters())
@@ -16,8 +30,8 @@ for p in ps:
     p.grad = torch.randn_like(p) * 1e-3
 
 
-def timed(fn, it=20):
-    for _ in range(3):
+def timed(fn, it=20, warm=3):
+    for _ in range(warm):
         fn()
     torch.cuda.synchronize()
     e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -28,6 +42,36 @@ def timed(fn, it=20):
     e[1].synchronize()
     return e[0].elapsed_time(e[1]) / it
 
+
+def three_groups(**kw):
+    named = list(m.named_parameters())
+    emb = [p for k, p in named if "embed" in k]
+    mats = [p for k, p in named if "embed" not in k and p.dim() >= 2]
+    vecs = [p for k, p in named if "embed" not in k and p.dim() < 2]
+    return FusedClipAdamW([{"params": mats, "weight_decay": 0.01}, {"params": vecs, "weight_decay": 0.0},
+                           {"params": emb, "weight_decay": 0.01, "decoupled": False, "clip": False, "lr": 2e-4}],
+                          lr=1e-4, max_grad_norm=1.0, schedule=LRSchedule("cosine", 100, 100000, 0.1), **kw)
+
+
+if args.adamw:
+    legs = [("mtts_clip_adam (FusedClipAdam)", FusedClipAdam(ps, lr=1e-4, max_grad_norm=1.0), 32),
+            ("mtts_clip_adamw, options off", FusedClipAdamW(ps, lr=1e-4, weight_decay=0.0, decoupled=False,
+                                                            max_grad_norm=1.0), 32),
+            ("mtts_clip_adamw, three groups", three_groups(), 32),
+            ("mtts_clip_adamw, three groups + EMA", three_groups(ema_decay=0.999), 40)]
+    times = {name: [] for name, _, _ in legs}
+    for name, opt, _ in legs:          # every shape warm before the first timed round
+        timed(opt.step, it=3)
+    for _ in range(args.rounds):
+        for name, opt, _ in legs:
+            times[name].append(timed(opt.step, it=100, warm=1))
+    print(f"params {n / 1e6:.1f} M, {args.rounds} interleaved rounds of 100 steps; median ms (min .. max)")
+    for name, _, nbytes in legs:
+        t = times[name]
+        med = statistics.median(t)
+        print(f"{name:<38} {med:.3f} ({min(t):.3f} .. {max(t):.3f})  {nbytes * n / med / 1e9:.2f} TB/s at "
+              f"{nbytes} B/param")
+    sys.exit(0)
 
 a = FusedClipAdam(ps, lr=1e-4, max_grad_norm=1.0)
 t1 = timed(a.step)
