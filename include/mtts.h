@@ -45,7 +45,9 @@ extern "C" {
  * struct.  So are the token log-probabilities: three symbols that take the
  * samplers' structs, byte for byte, and one new struct, MttsSampleLogprobOut.
  * So is the grouped optimizer step, mtts_clip_adamw, with its four structs:
- * MttsAdamTensor and mtts_clip_adam are untouched. */
+ * MttsAdamTensor and mtts_clip_adam are untouched.  So is the SMSD
+ * mixture-density head (csrc/mdn.hip): eight symbols and eight structs of
+ * its own; a binding that needs it checks that mtts_mixture_sample resolves. */
 #define MTTS_ABI_VERSION 15
 
 enum { MTTS_F32 = 0, MTTS_BF16 = 1 };
@@ -1229,6 +1231,190 @@ typedef struct {
 int mtts_sample_tokens_lp(const MttsSampleArgs* a, const MttsSampleLogprobOut* lp, void* stream);
 int mtts_sample_tokens_rows_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp, void* stream);
 int mtts_sample_tokens_slots_lp(const MttsSampleRowsArgs* a, const MttsSampleLogprobOut* lp, void* stream);
+
+/* ------------------------------------------------------------------------
+ * SMSD mixture-density head (ABI 15, additive; csrc/mdn.hip): the arithmetic
+ * of the reference's smsd.py between its three linear heads and the loss /
+ * the sampled style vector (MDNHead.forward :239-264, NoiseNet :277-292,
+ * mixture_nll_loss :295-372, SMSD.sample :127-164).  rows x K components x
+ * d style channels, 1 <= K <= MTTS_MDN_MAX_K, any d >= 1; dtype MTTS_F32 /
+ * MTTS_BF16 for every tensor of a call unless stated (fp32 math); rows are
+ * contiguous, `*_rs` are row strides in elements.  One workgroup per row, no
+ * atomics, every sum in a fixed order: bit-identical from run to run, and a
+ * row's result does not depend on the other rows of the launch.
+ *
+ * Variance modes, and sigma's elements per row:
+ *   MTTS_MDN_SHARED     "isotropic_across_clusters"  1      sigma (rows,)
+ *   MTTS_MDN_ISOTROPIC  "isotropic"                  K      sigma (rows, K)
+ *   MTTS_MDN_DIAGONAL   "diagonal"                   K * d  sigma (rows, K, d)
+ *   MTTS_MDN_FIXED      "fixed"                      none: variance 0.01, std 0.1;
+ *                                                    sigma pointers are ignored
+ * In MTTS_MDN_SHARED row b's variance serves every component of row b (the
+ * formula smsd.py:322 documents) at every batch size; the reference adds a
+ * (B,) term to a (B, K) one, which is that only for B == 1.
+ *
+ * Random numbers (sampler, and the NoiseNet eps when drawn): counter-based,
+ *   key      = mix64(seed_r + draw_r * golden)         mix64 = splitmix64's finalizer,
+ *   n(t, i)  = mix64((key ^ t * 0xD6E8FEB86659FD93) + i * golden) >> 40
+ *   u(t, i)  = (n + 0.5) * 2^-24                       golden = 0x9E3779B97F4A7C15
+ *   pick     : u(1, 0); the first k with u * total < cdf_k in k = 0 .. K-1,
+ *              cdf a sequential fp32 sum of pi, total its last value; else K-1
+ *   z[2j], z[2j+1] = r cos(t), r sin(t), r = sqrt(-2 ln u(2, j)), t = 2 pi u(3, j)
+ *   eps      : the same on streams 4, 5 with draw 0, i over the row's sigma_raw
+ * seed_r = seed[r] + *seed_in (64-bit wrap; seed_in optional): a function of
+ * (row seed, row draw count, stream, index) alone, so a row draws the same
+ * values in any row of any launch.
+ * ------------------------------------------------------------------------ */
+#define MTTS_MDN_MAX_K 32
+enum { MTTS_MDN_SHARED = 0, MTTS_MDN_ISOTROPIC = 1, MTTS_MDN_DIAGONAL = 2, MTTS_MDN_FIXED = 3 };
+enum { MTTS_MDN_NOISE_NONE = 0, MTTS_MDN_NOISE_GIVEN = 1, MTTS_MDN_NOISE_DRAWN = 2 };
+
+/* pi = softmax(pi_logits) over K; sigma = softplus(sigma_raw + noise_scale *
+ * eps), softplus in torch's threshold form (x for x > 20).  noise NONE: no
+ * term (eval); GIVEN: eps (rows, S) read; DRAWN: eps drawn from row_seed
+ * (+ *seed_in; seed_out receives the base used, for the backward's seed_in).
+ * MTTS_MDN_FIXED: only pi is computed, noise must be NONE.
+ * Backward: dlogits = pi (dpi - sum_k dpi_k pi_k), pi taken again from
+ * pi_logits (f.pi and f.sigma are checked like the forward's but not read);
+ * dsigma_raw = dsigma * sigmoid(pre-activation) (1 above 20); dnoise_scale[0]
+ * = sum dsigma_raw * eps over all rows (per-row partials in `workspace`,
+ * `rows` floats, then one workgroup in index order). */
+typedef struct {
+  int rows, K, d, mode;
+  int dtype;
+  int noise;                 /* MTTS_MDN_NOISE_* */
+  int64_t logits_rs, pi_rs, sraw_rs, sigma_rs, eps_rs;
+  const void* pi_logits;     /* (rows, K) */
+  const void* sigma_raw;     /* (rows, S) */
+  const void* eps;           /* (rows, S), noise GIVEN */
+  const float* noise_scale;  /* device fp32 scalar, noise != NONE */
+  const int64_t* row_seed;   /* (rows) device int64, noise DRAWN */
+  const int64_t* seed_in;    /* optional device int64 added to every row seed */
+  int64_t* seed_out;         /* optional: receives *seed_in */
+  void* pi;                  /* (rows, K) */
+  void* sigma;               /* (rows, S) */
+} MttsMdnParamsArgs;
+
+typedef struct {
+  MttsMdnParamsArgs f;
+  const void* dpi;
+  int64_t dpi_rs;
+  const void* dsigma;
+  int64_t dsigma_rs;
+  void* dlogits;
+  int64_t dlogits_rs;
+  void* dsigma_raw;
+  int64_t dsraw_rs;
+  float* dnoise_scale;       /* fp32 scalar; may be NULL when noise is NONE */
+  float* workspace;          /* rows floats */
+} MttsMdnParamsBwdArgs;
+
+int mtts_mdn_params_fwd(const MttsMdnParamsArgs* a, void* stream);
+int mtts_mdn_params_bwd(const MttsMdnParamsBwdArgs* a, void* stream);
+
+/* loss[0] = -mean_b lse_b, lse_b = logsumexp_k(log(pi_bk + 1e-8) + log N(y_b |
+ * mu_bk, var)), log N = -d/2 log(2 pi) - 1/2 sum_j log var - 1/2 sum_j (y_j -
+ * mu_kj)^2 / var.  lse (rows,) fp32 is saved for the backward, which writes
+ * dpi (rows, K), dmu (rows, K, d), dy (rows, d) and dsigma (sigma's shape;
+ * none in MTTS_MDN_FIXED), all scaled by grad_loss[0] (device fp32). */
+typedef struct {
+  int rows, K, d, mode;
+  int dtype;
+  int reserved_;
+  int64_t y_rs, pi_rs, mu_rs, sigma_rs;
+  const void* y;             /* (rows, d) */
+  const void* pi;            /* (rows, K) */
+  const void* mu;            /* (rows, K, d) */
+  const void* sigma;
+  float* loss;               /* fp32 scalar */
+  float* lse;                /* (rows) fp32 */
+} MttsMixtureNllArgs;
+
+typedef struct {
+  MttsMixtureNllArgs f;
+  const float* grad_loss;
+  void* dy;
+  int64_t dy_rs;
+  void* dpi;
+  int64_t dpi_rs;
+  void* dmu;
+  int64_t dmu_rs;
+  void* dsigma;
+  int64_t dsigma_rs;
+} MttsMixtureNllBwdArgs;
+
+int mtts_mixture_nll_fwd(const MttsMixtureNllArgs* a, void* stream);
+int mtts_mixture_nll_bwd(const MttsMixtureNllBwdArgs* a, void* stream);
+
+/* out[r] = mu[r, k_r] + std * z, k_r the row's pick (also written to
+ * component[r] when given); std = sigma[r] / sigma[r, k_r] / sigma[r, k_r, :]
+ * / 0.1 by mode. */
+typedef struct {
+  int rows, K, d, mode;
+  int dtype;
+  int reserved_;
+  int64_t pi_rs, mu_rs, sigma_rs, out_rs;
+  const void* pi;
+  const void* mu;
+  const void* sigma;
+  const int64_t* seed;       /* (rows) device int64 */
+  const int64_t* draw;       /* (rows) device int64 draw counts; NULL = 0 */
+  const int64_t* seed_in;    /* optional device int64 added to every row seed */
+  void* out;                 /* (rows, d) */
+  int* component;            /* optional (rows) int32 */
+} MttsMixtureSampleArgs;
+
+int mtts_mixture_sample(const MttsMixtureSampleArgs* a, void* stream);
+
+/* ReLU -> Dropout of the head's MLP in one pass.  Forward (y_fwd NULL):
+ * out = relu(x) * keep(i) / (1 - p) with mtts_dropout's mask of (seed [+
+ * *seed_in], i) (group 1) and its seed_in / seed_out; p = 0 is a plain ReLU.
+ * Backward (y_fwd = the forward's output, x = dy): out = y_fwd > 0 ? x / (1 -
+ * p) : 0; no seed is read.  Contiguous, 16-byte aligned, any n >= 0. */
+typedef struct {
+  int64_t n;
+  int dtype;
+  float p;
+  uint64_t seed;
+  const void* x;
+  const void* y_fwd;
+  void* out;
+  const int64_t* seed_in;
+  int64_t* seed_out;
+} MttsReluDropoutArgs;
+
+int mtts_relu_dropout(const MttsReluDropoutArgs* a, void* stream);
+
+/* LayerNorm over rows of any width, for the head's input at widths the
+ * LayerNorm above does not take (cols not a multiple of 64): y = (x - mean)
+ * rstd w + b, biased variance, rstd = 1 / sqrt(var + eps); w, b fp32; mean,
+ * rstd (rows) fp32 saved.  Backward: dx (x's dtype) and fp32 dw, db (cols),
+ * summed over the rows in index order. */
+typedef struct {
+  int rows, cols;
+  int dtype;
+  float eps;
+  int64_t x_rs, y_rs;
+  const void* x;
+  const float* w;
+  const float* b;
+  void* y;
+  float* mean;
+  float* rstd;
+} MttsRowLNArgs;
+
+typedef struct {
+  MttsRowLNArgs f;
+  const void* dy;
+  int64_t dy_rs;
+  void* dx;
+  int64_t dx_rs;
+  float* dw;
+  float* db;
+} MttsRowLNBwdArgs;
+
+int mtts_mdn_layernorm_fwd(const MttsRowLNArgs* a, void* stream);
+int mtts_mdn_layernorm_bwd(const MttsRowLNBwdArgs* a, void* stream);
 
 #ifdef __cplusplus
 }

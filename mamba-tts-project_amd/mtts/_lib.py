@@ -219,6 +219,56 @@ class AdamWArgs(C.Structure):
                 ("active_groups", C.c_uint64), ("total_chunks", i64), ("clip_chunks", i64), ("schedule", LrSchedule)]
 
 
+MDN_MAX_K = 32
+MDN_MODES = {"isotropic_across_clusters": 0, "isotropic": 1, "diagonal": 2, "fixed": 3}
+MDN_NOISE_NONE, MDN_NOISE_GIVEN, MDN_NOISE_DRAWN = 0, 1, 2
+
+
+class MdnParamsArgs(C.Structure):
+    _fields_ = [("rows", i32), ("K", i32), ("d", i32), ("mode", i32), ("dtype", i32), ("noise", i32),
+                ("logits_rs", i64), ("pi_rs", i64), ("sraw_rs", i64), ("sigma_rs", i64), ("eps_rs", i64),
+                ("pi_logits", vp), ("sigma_raw", vp), ("eps", vp), ("noise_scale", vp), ("row_seed", vp),
+                ("seed_in", vp), ("seed_out", vp), ("pi", vp), ("sigma", vp)]
+
+
+class MdnParamsBwdArgs(C.Structure):
+    _fields_ = [("f", MdnParamsArgs), ("dpi", vp), ("dpi_rs", i64), ("dsigma", vp), ("dsigma_rs", i64),
+                ("dlogits", vp), ("dlogits_rs", i64), ("dsigma_raw", vp), ("dsraw_rs", i64),
+                ("dnoise_scale", vp), ("workspace", vp)]
+
+
+class MixtureNllArgs(C.Structure):
+    _fields_ = [("rows", i32), ("K", i32), ("d", i32), ("mode", i32), ("dtype", i32), ("reserved_", i32),
+                ("y_rs", i64), ("pi_rs", i64), ("mu_rs", i64), ("sigma_rs", i64),
+                ("y", vp), ("pi", vp), ("mu", vp), ("sigma", vp), ("loss", vp), ("lse", vp)]
+
+
+class MixtureNllBwdArgs(C.Structure):
+    _fields_ = [("f", MixtureNllArgs), ("grad_loss", vp), ("dy", vp), ("dy_rs", i64), ("dpi", vp), ("dpi_rs", i64),
+                ("dmu", vp), ("dmu_rs", i64), ("dsigma", vp), ("dsigma_rs", i64)]
+
+
+class MixtureSampleArgs(C.Structure):
+    _fields_ = [("rows", i32), ("K", i32), ("d", i32), ("mode", i32), ("dtype", i32), ("reserved_", i32),
+                ("pi_rs", i64), ("mu_rs", i64), ("sigma_rs", i64), ("out_rs", i64),
+                ("pi", vp), ("mu", vp), ("sigma", vp), ("seed", vp), ("draw", vp), ("seed_in", vp),
+                ("out", vp), ("component", vp)]
+
+
+class ReluDropoutArgs(C.Structure):
+    _fields_ = [("n", i64), ("dtype", i32), ("p", f32), ("seed", C.c_uint64), ("x", vp), ("y_fwd", vp), ("out", vp),
+                ("seed_in", vp), ("seed_out", vp)]
+
+
+class RowLNArgs(C.Structure):
+    _fields_ = [("rows", i32), ("cols", i32), ("dtype", i32), ("eps", f32), ("x_rs", i64), ("y_rs", i64),
+                ("x", vp), ("w", vp), ("b", vp), ("y", vp), ("mean", vp), ("rstd", vp)]
+
+
+class RowLNBwdArgs(C.Structure):
+    _fields_ = [("f", RowLNArgs), ("dy", vp), ("dy_rs", i64), ("dx", vp), ("dx_rs", i64), ("dw", vp), ("db", vp)]
+
+
 _SIGS = {
     "mtts_abi_version": ([], i32),
     "mtts_last_error": ([], C.c_char_p),
@@ -283,6 +333,14 @@ _SIGS = {
     "mtts_sample_tokens_lp": ([C.POINTER(SampleArgs), C.POINTER(SampleLogprobOut), vp], i32),
     "mtts_sample_tokens_rows_lp": ([C.POINTER(SampleRowsArgs), C.POINTER(SampleLogprobOut), vp], i32),
     "mtts_sample_tokens_slots_lp": ([C.POINTER(SampleRowsArgs), C.POINTER(SampleLogprobOut), vp], i32),
+    "mtts_mdn_params_fwd": ([C.POINTER(MdnParamsArgs), vp], i32),
+    "mtts_mdn_params_bwd": ([C.POINTER(MdnParamsBwdArgs), vp], i32),
+    "mtts_mixture_nll_fwd": ([C.POINTER(MixtureNllArgs), vp], i32),
+    "mtts_mixture_nll_bwd": ([C.POINTER(MixtureNllBwdArgs), vp], i32),
+    "mtts_mixture_sample": ([C.POINTER(MixtureSampleArgs), vp], i32),
+    "mtts_relu_dropout": ([C.POINTER(ReluDropoutArgs), vp], i32),
+    "mtts_mdn_layernorm_fwd": ([C.POINTER(RowLNArgs), vp], i32),
+    "mtts_mdn_layernorm_bwd": ([C.POINTER(RowLNBwdArgs), vp], i32),
 }
 
 _lib = None
@@ -306,7 +364,8 @@ def lib():
                           ("mtts_sample_tokens_slots_lp", "token log-probabilities"),
                           ("mtts_attention_decode_split_shared", "shared-key samples"),
                           ("mtts_attention_decode_split_fp8", "FP8 conditioning K/V"),
-                          ("mtts_clip_adamw", "grouped AdamW step")):
+                          ("mtts_clip_adamw", "grouped AdamW step"),
+                          ("mtts_mixture_sample", "SMSD mixture-density head")):
             if not hasattr(L, sym):
                 raise RuntimeError(f"{LIB_PATH} is stale: it was built before {sym} ({what}) was "
                                    "added; rebuild it with __graft_entry__.build() "

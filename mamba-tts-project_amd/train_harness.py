@@ -10,6 +10,10 @@ order and with its semantics:
   text_encoder(phoneme_ids, mask True = pad)                    :187-188
   loss_smsd = 0 (spk_embs None), style_emb = a fixed synthetic
   z_style in place of smsd(style_prompts) (no_grad)             :190-195
+  -- or, with TrainStep(smsd=...) and a batch that holds precomputed
+  [CLS] vectors `style_cls` and speaker embeddings `spk_emb`:
+  loss_smsd = smsd(style_cls, y_true=spk_emb), style_emb =
+  smsd(style_cls) under no_grad, on the drop-in smsd.py
   dur_predictor -> heuristic_durations -> compute_loss           :197-203
   style_pipe(text_hidden, style_emb, exp(log_dur).detach())     :205-210
   (its outputs are dead in train.py: they enter no loss)
@@ -115,8 +119,12 @@ class TrainStep:
     length read, which the reference makes too)."""
 
     def __init__(self, models: C5Models, lr=1e-4, w_codec=1.0, w_dur=0.1, w_smsd=0.5, grad_allreduce=None,
-                 train_mode=True, one_optimizer=False):
-        """one_optimizer: the same update from one FusedClipAdamW with two
+                 train_mode=True, one_optimizer=False, smsd=None):
+        """smsd: an smsd.SMSD(bert_model=None) (optional): the step's third
+        loss term and its sampled style vector come from it when the batch
+        holds `style_cls` (B, bert_dim) and `spk_emb` (B, d_style); its head's
+        parameters join the unclipped optimizer group.
+        one_optimizer: the same update from one FusedClipAdamW with two
         groups (decoder clipped, the rest not; both L2 with weight_decay 0):
         three launches and one descriptor plan instead of six and two."""
         self.m = models
@@ -126,6 +134,10 @@ class TrainStep:
         dec_params = list(models.decoder.parameters())
         rest = [p for mod in (models.text_encoder, models.dur_predictor, models.style_pipe)
                 for p in mod.parameters() if p.requires_grad]
+        self.smsd = smsd
+        if smsd is not None:
+            smsd.train(train_mode)
+            rest += [p for p in smsd.mdn_head.parameters() if p.requires_grad]
         self.opt = None
         if one_optimizer:
             self.opt = FusedClipAdamW([{"params": dec_params, "clip": True}, {"params": rest, "clip": False}], lr=lr,
@@ -146,6 +158,10 @@ class TrainStep:
         text_hidden = enc(ids, mask=text_mask)                                     # :188
         loss_smsd = torch.zeros((), device=codec.device)                          # :192 (spk_embs None)
         style_emb = batch["style_emb"]                                            # :193-195 (no_grad there)
+        if self.smsd is not None and "style_cls" in batch and "spk_emb" in batch:
+            loss_smsd = self.smsd(batch["style_cls"], y_true=batch["spk_emb"])    # :192
+            with torch.no_grad():
+                style_emb = self.smsd(batch["style_cls"])                         # :193-194
         log_dur_pred = dur(text_hidden, mask=text_mask)                            # :198
         durations_target = heuristic_durations(text_mask, audio_tokens.shape[1])   # :201
         loss_dur = dur.compute_loss(log_dur_pred, durations_target, mask=text_mask)
@@ -185,4 +201,4 @@ class TrainStep:
         total, lc, ld, ls, _ = self.losses(batch)
         self.backward(total)
         self.optimizer_step()
-        return {"loss_total": total.detach(), "codec": lc.detach(), "dur": ld.detach(), "smsd": ls}
+        return {"loss_total": total.detach(), "codec": lc.detach(), "dur": ld.detach(), "smsd": ls.detach()}
