@@ -26,6 +26,17 @@ __global__ void conv_update_kernel(const MttsConvUpdateArgs a) {
   stf((T*)a.out + (int64_t)b * a.out_bs + c, v);
 }
 
+// softplus accurate relative to its result.  common.h's softplus_f forms
+// log(1 + e) with the sum rounded to fp32: eps absolute, which at the steps a
+// trained layer takes (softplus(dt_bias) 1e-3 .. 1e-1) is 10 .. 1000 eps of dt
+// and moved the state by 60 .. 110 eps of its condition (tests/step_ref.py).
+// One evaluation per (batch, channel), so log1pf's polynomial costs nothing
+// beside the state row's traffic.
+__device__ __forceinline__ float softplus_step(float x) {
+  const float e = __builtin_amdgcn_exp2f(fminf(x, 20.f) * kLog2e);
+  return x > 20.f ? x : log1pf(e);
+}
+
 // Four lanes per (batch, channel), lane j owning states 4j..4j+3: a wave's
 // state / A loads and state stores are 1 KiB contiguous (one 16-byte piece
 // per lane), the fused dt_proj dot is split over the quad (a quarter of
@@ -82,7 +93,7 @@ __global__ void state_update_kernel(const MttsStateUpdateArgs a) {
     dt = ldf((const Tio*)a.dt + (int64_t)b * a.dt_bs + c);
   }
   dt += a.dt_bias ? a.dt_bias[c] : 0.f;
-  if (a.dt_softplus) dt = softplus_f(dt);
+  if (a.dt_softplus) dt = softplus_step(dt);
   const float dtx = dt * x;
   float h[4] = {s.x, s.y, s.z, s.w};
   const float Av[4] = {A.x, A.y, A.z, A.w};

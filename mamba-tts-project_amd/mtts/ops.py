@@ -275,15 +275,40 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
 # ---------------------------------------------------------------------------
 # decode step
 # ---------------------------------------------------------------------------
+def _step_arg(fn, name, t, dtype=torch.float32, shape=None, contiguous=True):
+    """A decode-step kernel reads `t` raw: say what is wrong with it.  The
+    states are updated in place and the fp32 parameters are read every step,
+    so nothing here is converted (the upstream-signature shims below convert)."""
+    if t.dtype != dtype:
+        raise TypeError(f"{fn}: {name} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{fn}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{fn}: {name} must be contiguous")
+    if not contiguous and t.stride(-1) != 1:
+        raise ValueError(f"{fn}: {name} needs unit element stride")
+
+
 def conv_update(x, conv_state, w, bias=None, silu=True, out=None):
-    """x (B, D); conv_state (B, D, K) fp32 updated IN PLACE.  Returns out (B, D)."""
-    _check_cuda(x, conv_state, w)
+    """x (B, D); conv_state (B, D, K) fp32 contiguous, updated IN PLACE; w
+    (D, K) and bias (D,) fp32 contiguous.  Returns out (B, D) in x's dtype
+    (`out`, if given, may be a row-strided view)."""
+    _check_cuda(x, conv_state, w, bias, out)
     Bsz, Dm = x.shape
     if x.stride(-1) != 1:
         x = x.contiguous()
-    out = torch.empty(Bsz, Dm, device=x.device, dtype=x.dtype) if out is None else out
+    K = conv_state.shape[-1]
+    fn = "conv_update"
+    _step_arg(fn, "conv_state", conv_state, shape=(Bsz, Dm, K))
+    _step_arg(fn, "w", w, shape=(Dm, K))
+    if bias is not None:
+        _step_arg(fn, "bias", bias, shape=(Dm,))
+    if out is None:
+        out = torch.empty(Bsz, Dm, device=x.device, dtype=x.dtype)
+    else:
+        _step_arg(fn, "out", out, x.dtype, (Bsz, Dm), contiguous=False)
     a = L.ConvUpdateArgs()
-    a.batch, a.dim, a.width, a.dtype, a.silu = Bsz, Dm, conv_state.shape[-1], L.dtype_code(x), int(silu)
+    a.batch, a.dim, a.width, a.dtype, a.silu = Bsz, Dm, K, L.dtype_code(x), int(silu)
     a.x_bs, a.out_bs = x.stride(0), out.stride(0)
     a.x, a.conv_state, a.w, a.bias, a.out = x.data_ptr(), conv_state.data_ptr(), w.data_ptr(), L.ptr(bias), out.data_ptr()
     L.call("mtts_causal_conv1d_update", a)
@@ -292,20 +317,42 @@ def conv_update(x, conv_state, w, bias=None, silu=True, out=None):
 
 def state_update(state, x, dt, A, Bm, Cm, D=None, z=None, dt_bias=None, softplus=True, out=None, dt_w=None,
                  packed_out=False):
-    """state (B, D, N) fp32 updated IN PLACE; x/z (B, D); Bm/Cm (B, N) with
-    unit element stride; dt (B, D) raw delta, or with dt_w (D, R) given the
-    (B, R) low-rank input of dt_proj (fused: delta = dt @ dt_w.t()).
+    """state (B, D, N) fp32 contiguous, updated IN PLACE; x/z (B, D) of one
+    dtype (row-strided views allowed); Bm/Cm (B, N) with unit element stride
+    (Cm is converted to Bm's dtype, as scan_fwd does); A (D, N), D and dt_bias
+    (D,) fp32 contiguous; dt (B, D) raw delta in x's dtype, or with dt_w (D, R)
+    given the (B, R) low-rank input of dt_proj (fused: delta = dt @ dt_w.t()).
     packed_out: y is returned ONLY as a PackedAct (out_proj's operand)."""
-    _check_cuda(state, x, dt, A, Bm, Cm, dt_w)
-    for t in (Bm, Cm, dt):
-        if t.stride(-1) != 1:
-            raise ValueError("state_update: B / C / dt need unit element stride")
+    _check_cuda(state, x, dt, A, Bm, Cm, D, z, dt_bias, out, dt_w)
+    fn = "state_update"
     Bsz, Dm = x.shape
+    Ns = state.shape[-1]
+    if Cm.dtype != Bm.dtype:
+        Cm = Cm.to(Bm.dtype)
+    _step_arg(fn, "state", state, shape=(Bsz, Dm, Ns))
+    _step_arg(fn, "A", A, shape=(Dm, Ns))
+    _step_arg(fn, "x", x, x.dtype, contiguous=False)
+    _step_arg(fn, "Bm", Bm, Bm.dtype, (Bsz, Ns), contiguous=False)
+    _step_arg(fn, "Cm", Cm, Bm.dtype, (Bsz, Ns), contiguous=False)
+    if D is not None:
+        _step_arg(fn, "D", D, shape=(Dm,))
+    if dt_bias is not None:
+        _step_arg(fn, "dt_bias", dt_bias, shape=(Dm,))
+    if z is not None:
+        _step_arg(fn, "z", z, x.dtype, (Bsz, Dm), contiguous=False)
+    if dt_w is None:
+        _step_arg(fn, "dt", dt, x.dtype, (Bsz, Dm), contiguous=False)
+    else:
+        _step_arg(fn, "dt_w", dt_w, x.dtype, (Dm, dt_w.shape[-1]))
+        _step_arg(fn, "dt", dt, x.dtype, (Bsz, dt_w.shape[-1]), contiguous=False)
     yp = PackedAct.empty(Bsz, Dm, x.device) if packed_out else None
     if not packed_out:
-        out = torch.empty(Bsz, Dm, device=x.device, dtype=x.dtype) if out is None else out
+        if out is None:
+            out = torch.empty(Bsz, Dm, device=x.device, dtype=x.dtype)
+        else:
+            _step_arg(fn, "out", out, x.dtype, (Bsz, Dm), contiguous=False)
     a = L.StateUpdateArgs()
-    a.batch, a.dim, a.dstate = Bsz, Dm, state.shape[-1]
+    a.batch, a.dim, a.dstate = Bsz, Dm, Ns
     a.dtype_io, a.dtype_bc, a.dt_softplus = L.dtype_code(x), L.dtype_code(Bm), int(softplus)
     a.x_bs, a.dt_bs, a.B_bs, a.C_bs = x.stride(0), dt.stride(0), Bm.stride(0), Cm.stride(0)
     a.out_bs = 0 if out is None else out.stride(0)
@@ -316,8 +363,6 @@ def state_update(state, x, dt, A, Bm, Cm, D=None, z=None, dt_bias=None, softplus
     if yp is not None:
         a.out_packed = yp.data.data_ptr()
     if dt_w is not None:
-        if dt_w.dtype != x.dtype or dt_w.shape != (Dm, dt.shape[1]) or not dt_w.is_contiguous() or dt.dtype != x.dtype:
-            raise ValueError("state_update: dt_w must be a contiguous (D, R) tensor of x's dtype")
         a.dt_rank, a.dt_w = dt_w.shape[1], dt_w.data_ptr()
     L.call("mtts_selective_state_update", a)
     return out if yp is None else yp
